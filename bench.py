@@ -10,9 +10,12 @@ on the data path (subframes are independent); the only cross-rank traffic is the
 max-over-ranks of the elapsed time.  value = total decoded bits of CRC-OK TBs on all ranks / max
 elapsed -> scaling "weak".
 
-Prints ONE JSON line on rank 0 (driver contract), including the dominant kernel's roofline (HIP
-events on the stream the kernels run on, averaged over the timed steps) and the CPU baseline
-(the oracle, i.e. this repo's CPU restatement of the chain, timed on a bounded sample on rank 0).
+Prints ONE JSON line on rank 0 (driver contract).  A plain run does only what the headline needs: it sets up, warms
+up, times the steps, checks the last step's CRC verdicts and payloads, writes them with --dump-outputs DIR, and
+prints the line.  --full adds every block that takes runs of its own: the dominant kernel's roofline from isolated
+launches (HIP events on the stream the kernels run on), the waterfall (`iterating`), PCIe-inclusive (`h2d`),
+`planning` and per-TTI (`tti`) blocks, and the CPU baseline (the oracle, i.e. this repo's CPU restatement of the
+chain, timed on a bounded sample on rank 0).
 """
 import argparse
 import concurrent.futures as cf
@@ -162,6 +165,40 @@ def emit(out):
     else:
         sys.stdout.flush()
         os.write(_LINE_FD, line)
+
+
+DUMP_SAMPLE_BYTES = 48 << 20   # --dump-outputs: the sampled rows' share of the 64 MB a dump may take
+DUMP_SEED = 0xD0
+
+
+def dump_rows(n, width):
+    """The rows of an n x width output that --dump-outputs writes as float32: all of them when they fit in
+    DUMP_SAMPLE_BYTES, else a fixed, seeded sample (sorted indices, the same for every run and build)."""
+    k = min(n, max(1, DUMP_SAMPLE_BYTES // (4 * width)))
+    if k == n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: DIR/<name>.npy for each array, as float32."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
+def batch_outputs(b, crc, pay):
+    """What a caller of one batch run receives (--dump-outputs): per TB the CRC verdict and the turbo iterations, and
+    the payload bytes of the dump_rows() TBs, one row per TB (zero-padded to the longest TB of the batch)."""
+    B = len(b.cfgs)
+    width = max(c.tbs // 8 for c in b.cfgs)
+    rows = dump_rows(B, width)
+    out = np.zeros((len(rows), width), np.float32)
+    for r, i in enumerate(rows):
+        p = b.payload(int(i), pay)
+        out[r, :len(p)] = p
+    return {"tb_crc": crc, "tb_iterations": b.download(abi.BUF_TB_ITS, np.uint32)[:B], "payload_sample": out,
+            "payload_sample_tb_index": rows}
 
 
 _STREAMS = []
@@ -466,7 +503,13 @@ def bench_codeblocks(args, world, rank, dev):
     per = [t.stage_ms() for t in tbs[:min(S, args.steps)]]
     nprof = sum(k for _, k in per)
     stage = {key: sum(st[key] * k for st, k in per) / nprof for key in per[0][0]}
-    iso = isolated_stages(tb, lambda: tb.run(d.data_ptr(), sptr[0]), dev, S, args.steps)
+    if args.dump_outputs and rank == 0:
+        ldec, lits, _ = tbs[(args.steps - 1) % S].results()   # the workspace the last timed step ran on
+        rows = dump_rows(n, K)
+        dump_outputs(args.dump_outputs,
+                     {"cb_bits_sample": ldec[rows], "cb_sample_index": rows, "cb_iterations": lits})
+        del ldec
+    iso = isolated_stages(tb, lambda: tb.run(d.data_ptr(), sptr[0]), dev, S, args.steps) if args.full else None
     dec, its, _ = tb.results()
     for k, t in enumerate(tbs[1:min(S, args.steps)], 1):
         assert np.array_equal(t.results()[0][:pool], dec[:pool]), f"stream {k} decoded differently"
@@ -488,10 +531,11 @@ def bench_codeblocks(args, world, rank, dev):
                       "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
                       "turbo_schedule": SCHED_DESC[tb.turbo_sched]},
            "turbo_codeblocks_per_s": round(cbps, 1), "ber": ber, "stage_ms_per_step": {k: round(v, 4) for k, v in stage.items()},
-           "roofline": {"kernel": tdec_kernel_name(tb.turbo_sched), "bound": "hbm", "achieved": round(ach, 2),
-                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": None,
-                        "algorithmic_bytes_per_launch": ab, **roofline_timing(stage, nprof, iso)},
            "rank_devices": devices}
+    if args.full or S == 1:   # a per-kernel figure needs the launches alone on the GPU (main(): the same rule)
+        out["roofline"] = {"kernel": tdec_kernel_name(tb.turbo_sched), "bound": "hbm", "achieved": round(ach, 2),
+                           "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": None,
+                           "algorithmic_bytes_per_launch": ab, **roofline_timing(stage, nprof, iso)}
     # the CPU baseline: rank 0, after the reduction (outside the timed region), at every N
     if not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -732,10 +776,11 @@ def bench_h2d(args, cfgs, pool_iq, batch, bits_ok, iq=None, steps=None):
                     "stream overlapped with the previous batch's decode"}
 
 
-def measure(args, cfgs, pool_iq, pool_tb, world, dev, steps, warmup):
+def measure(args, cfgs, pool_iq, pool_tb, world, dev, steps, warmup, dump=None):
     """Plan the batch, stage the pool in HBM (replicated on device into the batch IQ layout), run `warmup` untimed
     and `steps` timed passes (barrier + synchronize on both sides), then check the last step's outputs: every TB's
-    CRC verdict and, for every CRC-OK TB, its payload against the transmitted bytes.
+    CRC verdict and, for every CRC-OK TB, its payload against the transmitted bytes.  dump: a directory that the last
+    timed step's outputs (batch_outputs) are written to.
 
     --streams S > 1: S workspaces (abi.Batch) of the same batch on S HIP streams, consecutive steps issued
     round-robin -- a streaming receiver's double (triple) buffering: step i + 1's front end (OFDM, channel
@@ -800,13 +845,20 @@ def measure(args, cfgs, pool_iq, pool_tb, world, dev, steps, warmup):
     per = [(b.stage_ms(), b) for b in batches[:min(S, steps)]]
     nprof = sum(n for (_, n), _ in per)
     stage = {k: sum(st[k] * n for (st, n), _ in per) / nprof for k in per[0][0][0]}
-    iso = isolated_stages(batch, lambda: batch.run(d_iq.data_ptr(), sptr[0]), dev, S, steps)
+    # --full: the roofline's isolated launches (a re-run of the same inputs: the outputs checked below do not change)
+    iso = isolated_stages(batch, lambda: batch.run(d_iq.data_ptr(), sptr[0]), dev, S, steps) if args.full else None
     del d_iq
     bad, n_ok, its, bits_ok = 0, 0, None, 0.0
     for k, b in enumerate(batches[:min(S, steps)]):
         crc = b.download(abi.BUF_TB_CRC, np.uint32)[:B]
         pay = b.download(abi.BUF_PAYLOAD, np.uint8)
         bad += sum(int(not np.array_equal(b.payload(i, pay), pool_tb[i % len(pool_tb)])) for i in range(B) if crc[i])
+        if dump and k == (steps - 1) % S:   # the workspace the last timed step ran on
+            # written at once, before any workspace is closed: a 264-element array kept until after the closes was seen
+            # with one element overwritten on the host (value 2 at index 212, 4 of 8 runs) while three downloads of the
+            # same buffer before the closes all held 1 -- a stray host write during teardown, cause not found; `its`
+            # below, kept as long, showed the same once (mean_turbo_iterations 265 / 264)
+            dump_outputs(dump, batch_outputs(b, crc, pay))
         if k == 0:
             its = b.download(abi.BUF_TB_ITS, np.uint32)[:B]
             n_ok = int(crc.sum())
@@ -1166,6 +1218,15 @@ def main():
     # 200 steps (~2.4 s of decoding at the headline): long enough for an outside GPU-activity sampler to see
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every block beside the headline: the roofline's isolated launches, the waterfall "
+                         "(`iterating`), `h2d`, `planning` and `tti` blocks and the CPU baseline (each still under its own "
+                         "option: --iterating-snr, --h2d-steps, --plan-steps, --tti-ttis, --no-cpu-baseline); without it "
+                         "the run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): "
+                         "every TB's CRC verdict and iteration count, and the payload bytes of a fixed, seeded sample of "
+                         "the TBs (config 1: decoded bits of a sample of the code blocks, and iteration counts)")
     ap.add_argument("--sf-per-gpu", type=int, default=12500, help="subframes per GPU per step")
     ap.add_argument("--pool", type=int, default=256, help="distinct synthetic subframes per rank")
     ap.add_argument("--snr", type=float, default=30.0)
@@ -1239,6 +1300,10 @@ def main():
                          "and the device gather run over RCCL as in the N-GPU line (launch with WORLD_SIZE=1, MASTER_*)")
     ap.add_argument("--dry-run-llr", default=None, help=argparse.SUPPRESS)   # CPU launch rehearsal (tests only)
     args = ap.parse_args()
+    if not args.full:
+        # a plain run times the headline only: every block that takes runs of its own is off (measure() and
+        # bench_codeblocks() skip the roofline's isolated launches on args.full themselves)
+        args.no_cpu_baseline, args.iterating_snr, args.plan_steps, args.h2d_steps, args.tti_ttis = True, 0.0, 0, 0, 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))                     # before anything touches the GPU
     if args.streams <= 0:
@@ -1298,7 +1363,8 @@ def main():
         P = B                                               # every mixed subframe is distinct
     h = [0.8 + 0.3j, -0.4 + 0.5j] if args.config == 3 else None
     pool_iq, pool_tb = make_pool(cfgs[:P], args.snr, threads, first, h)
-    m = measure(args, cfgs, pool_iq, pool_tb, world, dev, args.steps, args.warmup)
+    m = measure(args, cfgs, pool_iq, pool_tb, world, dev, args.steps, args.warmup,
+                dump=args.dump_outputs if rank == 0 else None)
     batch, stage, nprof, elapsed = m["batch"], m["stage"], m["nprof"], m["elapsed"]
     n_ok, its, bad, bits_ok = m["n_ok"], m["its"], m["bad"], m["bits_ok"]
     # global counters: CRC-OK bits, code blocks, CRC-OK TBs, TB iterations, TBs, payload mismatches (every rank)
@@ -1370,11 +1436,15 @@ def main():
             "payload_mismatches_crc_ok": int(bad_all), "subframes_all_ranks": int(tb_all),
             "elapsed_per_rank_s": [round(x, 6) for x in per_rank], "rank_devices": devices,
             "stage_ms_per_step": {k: round(v, 4) for k, v in stage.items()},
-            "roofline": {"kernel": tdec_kernel_name(batch.turbo_sched), "bound": "hbm", "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": traffic, "valu_busy_pct": valu_busy, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": tdec_bytes, **roofline_timing(stage, nprof, m["iso"])},
         }
+        if args.full or max(1, args.streams) == 1:
+            # a per-kernel figure: the decoder's launches alone on the GPU (one stream, or --full's isolated launches);
+            # the overlapped steps of a plain run on several streams give none
+            out["roofline"] = {"kernel": tdec_kernel_name(batch.turbo_sched), "bound": "hbm",
+                               "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                               "valu_busy_pct": valu_busy, "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": tdec_bytes, **roofline_timing(stage, nprof, m["iso"])}
         if args.h2d:
             out["h2d"] = bench_h2d(args, cfgs, pool_iq, batch, bits_ok)
         elif args.config == 4 and args.h2d_steps > 0 and world == 1:

@@ -141,3 +141,21 @@ def test_static_workspaces_count(S, want):
     # every list is kept by some workspace, and every stream is used
     assert {k % 2 for k in range(W)} == {0, 1}
     assert {k % S for k in range(W)} == set(range(S))
+
+
+def test_dump_rows_and_outputs(tmp_path):
+    """--dump-outputs: small outputs are written whole, large ones as a fixed seeded sample of rows (the same on every
+    call, sorted, distinct) that keeps the dump under 64 MB; every file is float32 and holds the values given."""
+    assert np.array_equal(bench.dump_rows(256, 9422), np.arange(256))
+    r = bench.dump_rows(12500, 9422)
+    assert np.array_equal(r, bench.dump_rows(12500, 9422))
+    assert len(set(r.tolist())) == len(r) and np.all(np.diff(r) > 0) and r.min() >= 0 and r.max() < 12500
+    assert 1024 <= len(r) and len(r) * 9422 * 4 + 3 * 12500 * 4 <= 64 << 20
+    assert len(bench.dump_rows(65536, 6144)) * 6144 * 4 + 2 * 65536 * 4 <= 64 << 20
+    crc = np.array([1, 0, 1], np.uint32)
+    pay = np.arange(12, dtype=np.uint8).reshape(3, 4)
+    bench.dump_outputs(str(tmp_path / "d"), {"tb_crc": crc, "payload_sample": pay})
+    assert sorted(os.listdir(tmp_path / "d")) == ["payload_sample.npy", "tb_crc.npy"]
+    a, b = np.load(tmp_path / "d" / "tb_crc.npy"), np.load(tmp_path / "d" / "payload_sample.npy")
+    assert a.dtype == np.float32 and b.dtype == np.float32
+    assert np.array_equal(a, crc) and np.array_equal(b, pay)

@@ -94,7 +94,7 @@ def test_bench_spawns_its_own_ranks(built, tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dry-run-llr", str(path),
-                          "--cpu-seconds", "1.5"], env=env, capture_output=True, text=True, timeout=240)
+                          "--full", "--cpu-seconds", "1.5"], env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                   # only rank 0 prints
@@ -134,7 +134,7 @@ def test_bench_two_ranks_on_one_gpu(built):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--sf-per-gpu",
-                        "256", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1.5", "--iterating-snr", "0"],
+                        "256", "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "1.5", "--iterating-snr", "0"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -196,7 +196,7 @@ def test_bench_one_stream_full_line(built):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--sf-per-gpu", "256", "--steps", "4",
-                        "--warmup", "1", "--streams", "1", "--no-cpu-baseline", "--iterating-snr", "0",
+                        "--warmup", "1", "--streams", "1", "--full", "--no-cpu-baseline", "--iterating-snr", "0",
                         "--plan-steps", "4", "--h2d-steps", "2"],
                        cwd=root, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -209,6 +209,56 @@ def test_bench_one_stream_full_line(built):
         assert pl[k]["payload_mismatches_crc_ok"] == 0 and pl[k]["Mbps"] > 0, k
     assert all(b > 0 for b in pl["varied_static"]["crc_ok_bits_per_list"])
     assert set(d["h2d"]) >= {"sc16", "fc32"}
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dump(built, tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the headline only: the line has the headline's fields
+    for exactly N steps and none of the blocks that take runs of their own (those are --full's), and
+    `--dump-outputs DIR` writes the last timed step's outputs as float32 .npy files: every TB's CRC verdict and
+    iteration count, and the sampled TBs' payload bytes -- here equal to the transmitted bytes.
+
+    This shape once showed a 2 at TB 212 of the dumped verdicts (and of the iteration counts) in about half the runs:
+    not a device result (repeated downloads before the workspaces closed held 1) but a stray host write into an array
+    bench.py kept across the closes; the dump is now written before them (bench.py measure())."""
+    import json
+    import subprocess
+    import sys
+
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--sf-per-gpu", "264", "--dump-outputs", str(out)],
+                       cwd=root, env=env, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == bench.METRIC and d["unit"] == "Mbps" and d["higher_is_better"] is True
+    assert d["dtype"] == "f32+i16" and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["crc_ok_rate"] == 1.0 and d["payload_mismatches_crc_ok"] == 0 and d["subframes_all_ranks"] == 264
+    per = d["elapsed_per_rank_s"]
+    assert len(per) == 1 and abs(d["ms_per_step"] - per[0] / 3 * 1e3) < 1e-2
+    assert abs(d["value"] - 264 * 75376 * 3 / per[0] / 1e6) < 1e-3 * d["value"]
+    assert not {"iterating", "h2d", "planning", "tti", "cpu_baseline", "roofline"} & set(d)
+    files = {f: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert sorted(files) == ["payload_sample.npy", "payload_sample_tb_index.npy", "tb_crc.npy", "tb_iterations.npy"]
+    assert all(a.dtype == np.float32 for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    crc = files["tb_crc.npy"]
+    assert np.array_equal(crc, np.ones(264)), (np.flatnonzero(crc != 1).tolist(), crc[crc != 1].tolist(),
+                                               d["config"]["split_front_cu_eighths"], d["mean_turbo_iterations"])
+    assert np.array_equal(files["tb_iterations.npy"], np.ones(264))
+    idx = files["payload_sample_tb_index.npy"]
+    assert np.array_equal(idx, np.arange(264))               # a small shard is written whole
+    pay = files["payload_sample.npy"]
+    assert pay.shape == (264, 75376 // 8)
+    for i in (0, 1, 255, 256, 263):                          # subframe i carries pool entry i % 256
+        assert np.array_equal(pay[i], bench.tb_payload(i % 256, 75376 // 8)), i
 
 
 def test_native_stdout_prints_kept_off_the_line():

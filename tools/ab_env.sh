@@ -2,7 +2,7 @@
 # Same-box A/B of the library's creation-time environment knobs (engine.h Engine::Opts) on the bench:
 #   ./tools/ab_env.sh <tag> "<ENV=..>" "<ENV=..>" ...     ("-" = no extra variable); each setting runs twice,
 # interleaved (A B A B), one bench line per run (tools/bj.py).  Bench arguments: BENCH_ARGS (default: no CPU baseline,
-# no waterfall block, no planning / PCIe blocks; e.g. BENCH_ARGS="--no-cpu-baseline --plan-steps 0 --h2d-steps 0"
+# no waterfall block, no planning / PCIe blocks; e.g. BENCH_ARGS="--full --no-cpu-baseline --plan-steps 0 --h2d-steps 0 --tti-ttis 0"
 # keeps the waterfall block).
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}

@@ -15,7 +15,7 @@ cd $R
 for i in $(seq 1 $REPS); do
   for v in "${LIBS[@]}"; do
     if [ "$v" == "cur" ]; then lib=srsue_amd/libsrsue_amd.so; else lib=srsue_amd/libsrsue_amd_$v.so; fi
-    SRSUE_AMD_LIB=$lib timeout -k 10 300 python3 bench.py --no-cpu-baseline "$@" > $OUT/${v}_$i.json 2> $OUT/$v.err || exit 21
+    SRSUE_AMD_LIB=$lib timeout -k 10 300 python3 bench.py --full --no-cpu-baseline "$@" > $OUT/${v}_$i.json 2> $OUT/$v.err || exit 21
     echo -n "$v: "; python3 tools/bj.py $OUT/${v}_$i.json
   done
 done

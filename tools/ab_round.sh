@@ -7,7 +7,7 @@ mkdir -p $OUT
 for i in 1 2; do
   for v in $VS; do
     if [ $v = cur ]; then L=; else L=srsue_amd/libsrsue_amd_$v.so; fi
-    SRSUE_AMD_LIB=$L timeout -k 10 240 python3 bench.py --no-cpu-baseline "$@" > $OUT/${v}_$i.json 2> $OUT/$v.err || exit 20
+    SRSUE_AMD_LIB=$L timeout -k 10 240 python3 bench.py --full --no-cpu-baseline "$@" > $OUT/${v}_$i.json 2> $OUT/$v.err || exit 20
   done
 done
 echo done

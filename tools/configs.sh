@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$1
 mkdir -p $OUT
 cd $R
-run() { name=$1; shift; timeout -k 10 240 python3 bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || exit 20; }
+run() { name=$1; shift; timeout -k 10 240 python3 bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || exit 20; }
 run c2 --config 2 --cpu-seconds 6
 run c2_lane --config 2 --sched lane --no-cpu-baseline
 run c3 --config 3 --cpu-seconds 6

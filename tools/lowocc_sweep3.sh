@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$1
 mkdir -p $OUT
 cd $R
-run() { name=$1; shift; timeout -k 10 240 python3 bench.py --no-cpu-baseline "$@" > $OUT/$name.json 2> $OUT/$name.err || exit 20; echo -n "$name: "; python3 tools/bj.py $OUT/$name.json; }
+run() { name=$1; shift; timeout -k 10 240 python3 bench.py --full --no-cpu-baseline "$@" > $OUT/$name.json 2> $OUT/$name.err || exit 20; echo -n "$name: "; python3 tools/bj.py $OUT/$name.json; }
 run c3_s16_p2_h16 --config 3 --streams 16 --sched p2 --hw-queues 16
 run c3_s24_p2_h32 --config 3 --streams 24 --sched p2 --hw-queues 32
 run c3_s32_p2_h32 --config 3 --streams 32 --sched p2 --hw-queues 32

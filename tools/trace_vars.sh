@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 for i in 1 2; do
   for v in $VS; do
     if [ $v = cur ]; then L=; else L=$R/srsue_amd/libsrsue_amd_$v.so; fi
-    SRSUE_AMD_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${v}_$i -o run -- python3 $R/bench.py --no-cpu-baseline --iterating-snr 0 "$@" > $OUT/${v}_$i.json 2> $OUT/${v}_$i.err || exit 20
+    SRSUE_AMD_LIB=$L timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${v}_$i -o run -- python3 $R/bench.py --full --no-cpu-baseline --iterating-snr 0 "$@" > $OUT/${v}_$i.json 2> $OUT/${v}_$i.err || exit 20
   done
 done
 echo done
