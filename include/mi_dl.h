@@ -18,6 +18,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "srslte/common/timestamp.h"   /* srslte_timestamp_t of the receive callback (mi_acq_create) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -276,6 +278,90 @@ int        mi_sync_sss(mi_sync_t *s, const void *d_iq, const uint64_t *sf_off, c
 int        mi_sync_correct(mi_sync_t *s, const void *d_src, const uint64_t *src_off, void *d_dst,
                            const uint64_t *dst_off, const float *cfo, uint32_t n, uint32_t len, void *stream);
 int        mi_tx_sync(uint32_t cell_id, uint32_t nof_prb, uint32_t sf_idx, float amp, float *iq);
+
+/* ---- cell acquisition: PBCH / MIB decoding and cell search ----------------------------------
+ * What srsUE reaches through srslte_ue_mib_decode and srslte_ue_cellsearch_scan (phch_recv.cc:137-253), batched.
+ * Normal CP; cells with 1 or 2 CRS ports (a 4-port cell's MIB is reported as not found).
+ *
+ * PBCH (36.211 6.6, 36.212 5.3.1) over the grid and channel estimates a batch's front end (stages OFDM | CHEST)
+ * left in HBM, like mi_dl_ctrl_*.  Every subframe of the batch with sf_idx 0 is one PBCH frame (frame_of():
+ * its index, -1 for other subframes); any nof_prb.  run() enqueues up to two kernels (stage mask: 1 = soft
+ * bits, 2 = decode).  Stage 1 writes per frame and port hypothesis (0 = 1 port, 1 = 2 ports: SFBC, only where
+ * the subframe's cfg has nof_ports = 2) the 480 QPSK soft bits, not descrambled, at float
+ * (2 frame + hypothesis) * 480 of the soft-bit buffer.  Stage 2 decodes candidates: candidate c is n_frames[c]
+ * (1..4) consecutive radio frames of one cell given as batch subframe indices sf[4 c ..], oldest first.  For
+ * each it tries, in this order, f = 1..n_frames newest frames combined, then 1 port before 2, then the 40 ms
+ * phase of the newest frame sfn_offset = f-1..3 (at most 20 decodes), and reports the first whose CRC16 matches
+ * the port count's mask: found, nof_ports, sfn_offset, n_frames_used and the 24 MIB bits (unpack with
+ * srslte_pbch_mib_unpack; the newest frame's SFN is the unpacked sfn + sfn_offset).  set_candidates() checks
+ * every index (inside the batch, a subframe 0, one cell per candidate) and returns -1 before anything is
+ * launched; it leaves no candidates behind then.  result(): 1 found, 0 not found, -1 error.
+ * mi_pbch_re_indices: the 240 PBCH REs of a cell in mapping order (grid index l * 12 nof_prb + k), host only.
+ * mi_tx_pbch adds the PBCH quarter `phase` (0..3) of a BCH TTI carrying bch_payload to a subframe-0 IQ buffer
+ * (synthetic transmitter: nof_ports 1 or 2, flat per-port channel h, NULL = (1, 0); OFDM scaling of
+ * mi_tx_subframe, which leaves these REs empty). */
+typedef struct mi_pbch mi_pbch_t;
+typedef struct { uint32_t found, nof_ports, sfn_offset, n_frames_used; uint8_t bits[24]; } mi_pbch_result_t;
+int        mi_pbch_re_indices(uint32_t cell_id, uint32_t nof_prb, uint32_t re[240]);
+mi_pbch_t *mi_pbch_create(mi_dl_batch_t *b);
+void       mi_pbch_destroy(mi_pbch_t *p);
+uint32_t   mi_pbch_n_frames(const mi_pbch_t *p);
+int        mi_pbch_frame_of(const mi_pbch_t *p, uint32_t sf);
+int        mi_pbch_set_candidates(mi_pbch_t *p, const uint32_t *sf /* 4 per candidate */, const uint32_t *n_frames,
+                                  uint32_t n_cand);
+uint32_t   mi_pbch_n_jobs(const mi_pbch_t *p);   /* decodes the next run's stage 2 launches */
+int        mi_pbch_run(mi_pbch_t *p, uint32_t mask, void *stream);
+int        mi_pbch_result(mi_pbch_t *p, uint32_t cand, mi_pbch_result_t *out);
+size_t     mi_pbch_llr_floats(const mi_pbch_t *p);
+/* copy PBCH soft bits between host and device (upload != 0: host -> device) */
+int        mi_pbch_llr(mi_pbch_t *p, float *host, size_t n, int upload);
+int        mi_tx_pbch(uint32_t cell_id, uint32_t nof_prb, uint32_t nof_ports, const uint8_t bch_payload[24],
+                      uint32_t phase, const float *h_re_im, float *iq);
+
+/* Cell search over device-resident IQ at 1.92 Msps (6 PRB, N = 128; offsets in cf32 samples).  Window i is the
+ * 9600 + 128 samples at d_iq[off[i]] (5 ms and one symbol): every lag 0..9599 is correlated with each of the
+ * three PSS roots in chunks of 64 lags (one launch), and at each (window, root) peak the SSS is detected with
+ * the peak's CFO estimate (one launch) -- where its symbol lies inside the window (peak lag >= 137).  out[u]
+ * reports N_ID_2 = u over the windows, mirroring srslte_ue_cellsearch_result_t: cell_id = the most frequent
+ * 3 N_ID_1 + u (ties: the higher mean peak), mode = its share of the windows, peak = mean rho of the agreeing
+ * windows, psr = mean of peak / largest chunk maximum at least two chunks away from the peak's, cfo = mean
+ * estimate in subcarrier spacings, sf_start = stream offset of a subframe-0 boundary (the last one at or
+ * before the PSS's subframe of the newest agreeing window, plus whole frames if that lies before sample 0),
+ * found = peak > threshold.  threshold <= 0 selects MI_CELLSEARCH_THRESHOLD: rho of noise alone over N = 128
+ * samples is Beta(1, 127), so the chance that any of 3 x 9600 lags exceeds 0.2 is 28800 x 0.8^127 < 1e-7 per
+ * window, while a cell at 0 dB per RE gives rho near 0.3 (ue_sync.cpp's floor of 0.01 for a known cell lies
+ * inside the noise of a 128-sample window: the mean of Beta(1, 127) is 1/128).  Synchronous. */
+#define MI_CELLSEARCH_THRESHOLD 0.2f
+typedef struct mi_cellsearch mi_cellsearch_t;
+typedef struct { uint32_t found, cell_id; float mode, peak, psr, cfo; uint64_t sf_start; } mi_cell_result_t;
+mi_cellsearch_t *mi_cellsearch_create(void);
+void       mi_cellsearch_destroy(mi_cellsearch_t *s);
+int        mi_cellsearch_run(mi_cellsearch_t *s, const void *d_iq, const uint64_t *off, uint32_t n_windows,
+                             float threshold, mi_cell_result_t out[3], void *stream);
+
+/* Streaming acquisition over a receive callback at 1.92 Msps (the callback of srslte_ue_sync_init: it fills
+ * nsamples cf32 and returns their number).  One instance per thread; the kernels and transfers of search() and
+ * mib() run on the instance's own stream (the table uploads when an instance or its internal batch is created
+ * are blocking copies).  search(): reads n_half_frames * 9600 + 128 samples, runs the cell search above
+ * over them (sf_start counts samples since the instance was created) and consumes n_half_frames * 9600 of
+ * them; returns the number of cells found (0..3, *best = the found N_ID_2 with the highest peak) or -1.
+ * mib(): finds the cell's subframe 0 (PSS of cell_id mod 3 over a half frame, SSS check, as srslte_ue_sync's
+ * find; up to 8 half frames), then per radio frame reads that subframe, removes the CFO (`cfo` in subcarrier
+ * spacings, as search() reports it), runs OFDM + channel estimation on an internal 6-PRB 2-port slot, keeps the
+ * last four frames' soft bits and decodes the growing candidate (1, 2, 3, 4 frames); stops at the first MIB
+ * found or after max_frames.  Returns 1 found, 0 not found, -1 error.  mi_mib_t: the unpacked MIB, the port
+ * count from the CRC mask, the 10-bit SFN of the frame it stopped on, that frame's subframe-0 stream index and
+ * how many frames were read.  The frame timing is not tracked between frames (acquisition takes a few frames). */
+typedef struct mi_acq mi_acq_t;
+typedef struct {
+  uint32_t nof_prb, nof_ports, phich_length, phich_resources, sfn, n_frames;
+  uint64_t sf_start;
+  uint8_t  bits[24];
+} mi_mib_t;
+mi_acq_t  *mi_acq_create(int (*recv)(void *, void *, uint32_t, srslte_timestamp_t *), void *handler);
+void       mi_acq_destroy(mi_acq_t *a);
+int        mi_acq_search(mi_acq_t *a, uint32_t n_half_frames, float threshold, mi_cell_result_t out[3], uint32_t *best);
+int        mi_acq_mib(mi_acq_t *a, uint32_t cell_id, float cfo, uint32_t max_frames, mi_mib_t *mib);
 
 /* ---- host-IQ streaming pipeline -------------------------------------
  * Double buffering for IQ that arrives in host memory (srsUE's sync thread writes the worker's

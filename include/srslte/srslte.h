@@ -424,8 +424,9 @@ SRSLTE_API int srslte_dci_rar_to_ul_grant(srslte_dci_rar_grant_t *rar, uint32_t 
  * call reads one subframe through the receive callback, re-times and re-estimates the CFO on the PSS
  * of subframes 0 and 5 (an exponential average, srslte_sync_set_em_alpha), corrects the CFO on the GPU
  * into input_buffer and returns 1.  get_cfo / set_cfo: Hz; get_sfo: mean timing drift in samples/s.
- * Cell search (srslte_ue_cellsearch_*), MIB decoding (srslte_ue_mib_*) and AGC stay in srsLTE;
- * start_agc() returns an error, set_agc_period() is accepted. */
+ * Cell search (srslte_ue_cellsearch_*), MIB decoding (srslte_ue_mib_*) and AGC stay in srsLTE under these
+ * names; the library's own cell search and PBCH / MIB decoding are available as mi_cellsearch_*, mi_pbch_* and
+ * mi_acq_* (mi_dl.h).  start_agc() returns an error, set_agc_period() is accepted. */
 typedef struct SRSLTE_API { float threshold; float em_alpha; } srslte_sync_t;
 typedef struct SRSLTE_API { float gain; } srslte_agc_t;
 typedef struct mi_ue_sync_ctx mi_ue_sync_ctx;

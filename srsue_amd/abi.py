@@ -123,6 +123,25 @@ def lib():
             "mi_dl_ctrl_llr": (C.c_int, [vp, vp, sz, C.c_int]),
             "mi_dl_ctrl_set_phich": (C.c_int, [vp, vp, vp]),
             "mi_dl_ctrl_phich": (C.c_int, [vp, u32, vp]),
+            "mi_pbch_re_indices": (C.c_int, [u32, u32, vp]),
+            "mi_pbch_create": (vp, [vp]),
+            "mi_pbch_destroy": (None, [vp]),
+            "mi_pbch_n_frames": (u32, [vp]),
+            "mi_pbch_frame_of": (C.c_int, [vp, u32]),
+            "mi_pbch_set_candidates": (C.c_int, [vp, vp, vp, u32]),
+            "mi_pbch_n_jobs": (u32, [vp]),
+            "mi_pbch_run": (C.c_int, [vp, u32, vp]),
+            "mi_pbch_result": (C.c_int, [vp, u32, vp]),
+            "mi_pbch_llr_floats": (sz, [vp]),
+            "mi_pbch_llr": (C.c_int, [vp, vp, sz, C.c_int]),
+            "mi_tx_pbch": (C.c_int, [u32, u32, u32, vp, u32, vp, vp]),
+            "mi_cellsearch_create": (vp, []),
+            "mi_cellsearch_destroy": (None, [vp]),
+            "mi_cellsearch_run": (C.c_int, [vp, vp, vp, u32, C.c_float, vp, vp]),
+            "mi_acq_create": (vp, [vp, vp]),
+            "mi_acq_destroy": (None, [vp]),
+            "mi_acq_search": (C.c_int, [vp, u32, C.c_float, vp, vp]),
+            "mi_acq_mib": (C.c_int, [vp, u32, C.c_float, u32, vp]),
             "mi_sync_create": (vp, [u32]),
             "mi_sync_destroy": (None, [vp]),
             "mi_sync_fft_size": (u32, [vp]),
@@ -454,6 +473,204 @@ class Ctrl:
     def close(self):
         if self.h:
             lib().mi_dl_ctrl_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PbchResult(C.Structure):
+    """mi_pbch_result_t"""
+    _fields_ = [("found", C.c_uint32), ("nof_ports", C.c_uint32), ("sfn_offset", C.c_uint32),
+                ("n_frames_used", C.c_uint32), ("bits", C.c_uint8 * 24)]
+
+
+def pbch_re_indices(cell_id, nof_prb):
+    """the 240 PBCH REs of a cell in mapping order (grid index l * 12 nof_prb + k); host only"""
+    re = np.zeros(240, np.uint32)
+    if lib().mi_pbch_re_indices(cell_id, nof_prb, re.ctypes.data):
+        raise RuntimeError("mi_pbch_re_indices: " + last_error())
+    return re
+
+
+def tx_pbch(cell_id, nof_prb, nof_ports, bits24, phase, iq, h=None):
+    """add the PBCH quarter `phase` of a BCH TTI carrying bits24 to a subframe-0 iq (float32 interleaved, in place)"""
+    assert iq.dtype == np.float32 and iq.flags.c_contiguous and len(iq) >= 2 * lib().mi_sf_len(nof_prb)
+    b = np.ascontiguousarray(bits24, np.uint8)
+    assert b.size == 24
+    hh = None
+    if h is not None:
+        hh = np.zeros(4, np.float32)
+        for p, v in enumerate(h[:2]):
+            hh[2 * p], hh[2 * p + 1] = v.real, v.imag
+    if lib().mi_tx_pbch(cell_id, nof_prb, nof_ports, b.ctypes.data, phase, None if hh is None else hh.ctypes.data,
+                        iq.ctypes.data):
+        raise RuntimeError("mi_tx_pbch: " + last_error())
+
+
+class Pbch:
+    """PBCH receiver over a batch's grid / channel estimates (mi_pbch_*): every subframe 0 of the batch is a frame."""
+    LLR, DECODE = 1, 2
+
+    def __init__(self, batch):
+        self.batch = batch
+        self.h = lib().mi_pbch_create(batch.h)
+        if not self.h:
+            raise RuntimeError("mi_pbch_create: " + last_error())
+        self.n_cand = 0
+
+    @property
+    def n_frames(self):
+        return lib().mi_pbch_n_frames(self.h)
+
+    @property
+    def n_jobs(self):
+        return lib().mi_pbch_n_jobs(self.h)
+
+    def frame_of(self, sf):
+        return lib().mi_pbch_frame_of(self.h, sf)
+
+    def set_candidates(self, cands):
+        """cands: per candidate the batch subframe indices of its 1..4 frames, oldest first"""
+        sf = np.zeros((max(len(cands), 1), 4), np.uint32)
+        n = np.zeros(max(len(cands), 1), np.uint32)
+        for i, c in enumerate(cands):
+            n[i] = len(c)
+            sf[i, :min(len(c), 4)] = list(c)[:4]
+        self.n_cand = 0
+        if lib().mi_pbch_set_candidates(self.h, sf.ctypes.data, n.ctypes.data, len(cands)):
+            raise RuntimeError("mi_pbch_set_candidates: " + last_error())
+        self.n_cand = len(cands)
+
+    def run(self, stream_ptr=None, mask=3):
+        if lib().mi_pbch_run(self.h, mask, C.c_void_p(stream_ptr or 0)):
+            raise RuntimeError("mi_pbch_run: " + last_error())
+
+    def result(self, cand):
+        """None, or (nof_ports, sfn_offset, n_frames_used, bits[24]) of the first decode that passed"""
+        r = PbchResult()
+        rc = lib().mi_pbch_result(self.h, cand, C.byref(r))
+        if rc < 0:
+            raise RuntimeError("mi_pbch_result: " + last_error())
+        return (r.nof_ports, r.sfn_offset, r.n_frames_used, np.array(r.bits[:], np.uint8)) if rc == 1 else None
+
+    def llr(self):
+        """soft bits [frame][hypothesis][480], not descrambled"""
+        n = lib().mi_pbch_llr_floats(self.h)
+        out = np.zeros(n, np.float32)
+        if n and lib().mi_pbch_llr(self.h, out.ctypes.data, n, 0):
+            raise RuntimeError("mi_pbch_llr: " + last_error())
+        return out.reshape(-1, 2, 480)
+
+    def set_llr(self, host):
+        a = np.ascontiguousarray(host, np.float32)
+        if lib().mi_pbch_llr(self.h, a.ctypes.data, a.size, 1):
+            raise RuntimeError("mi_pbch_llr: " + last_error())
+
+    def close(self):
+        if self.h:
+            lib().mi_pbch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CellResult(C.Structure):
+    """mi_cell_result_t"""
+    _fields_ = [("found", C.c_uint32), ("cell_id", C.c_uint32), ("mode", C.c_float), ("peak", C.c_float),
+                ("psr", C.c_float), ("cfo", C.c_float), ("sf_start", C.c_uint64)]
+
+
+class CellSearch:
+    """Cell search over device-resident 1.92 Msps IQ (mi_cellsearch_*): one result per N_ID_2."""
+    HALF = 9600
+
+    def __init__(self):
+        self.h = lib().mi_cellsearch_create()
+        if not self.h:
+            raise RuntimeError("mi_cellsearch_create: " + last_error())
+
+    def run(self, d_iq, offsets, threshold=0.0, stream_ptr=None):
+        off = np.ascontiguousarray(offsets, np.uint64)
+        out = (CellResult * 3)()
+        if lib().mi_cellsearch_run(self.h, C.c_void_p(d_iq), off.ctypes.data, len(off), threshold, out,
+                                   C.c_void_p(stream_ptr or 0)):
+            raise RuntimeError("mi_cellsearch_run: " + last_error())
+        return [dict(found=bool(r.found), cell_id=r.cell_id, mode=r.mode, peak=r.peak, psr=r.psr, cfo=r.cfo,
+                     sf_start=r.sf_start) for r in out]
+
+    def close(self):
+        if self.h:
+            lib().mi_cellsearch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Mib(C.Structure):
+    """mi_mib_t"""
+    _fields_ = [(n, C.c_uint32) for n in ("nof_prb", "nof_ports", "phich_length", "phich_resources", "sfn", "n_frames")] + \
+               [("sf_start", C.c_uint64), ("bits", C.c_uint8 * 24)]
+
+
+class Timestamp(C.Structure):
+    """srslte_timestamp_t"""
+    _fields_ = [("full_secs", C.c_long), ("frac_secs", C.c_double)]
+
+
+RECV_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(Timestamp))
+
+
+class Acq:
+    """Streaming acquisition over a receive callback at 1.92 Msps (mi_acq_*).  recv(n) returns n cf32 samples as
+    a float32 array of 2 n values, or None when the stream has ended."""
+
+    def __init__(self, recv):
+        def cb(handler, data, nsamples, ts):
+            x = recv(nsamples)
+            if x is None or len(x) < 2 * nsamples:
+                return -1
+            x = np.ascontiguousarray(x[:2 * nsamples], np.float32)
+            C.memmove(data, x.ctypes.data, 8 * nsamples)
+            return nsamples
+        self._cb = RECV_CB(cb)           # kept alive as long as the instance
+        self.h = lib().mi_acq_create(C.cast(self._cb, C.c_void_p), None)
+        if not self.h:
+            raise RuntimeError("mi_acq_create: " + last_error())
+
+    def search(self, n_half_frames, threshold=0.0):
+        """(results per N_ID_2 as CellSearch.run, best N_ID_2 or None)"""
+        out = (CellResult * 3)()
+        best = C.c_uint32()
+        rc = lib().mi_acq_search(self.h, n_half_frames, threshold, out, C.byref(best))
+        if rc < 0:
+            raise RuntimeError("mi_acq_search: " + last_error())
+        res = [dict(found=bool(r.found), cell_id=r.cell_id, mode=r.mode, peak=r.peak, psr=r.psr, cfo=r.cfo,
+                    sf_start=r.sf_start) for r in out]
+        return res, (best.value if rc > 0 else None)
+
+    def mib(self, cell_id, cfo, max_frames):
+        """the Mib found within max_frames radio frames, or None"""
+        m = Mib()
+        rc = lib().mi_acq_mib(self.h, cell_id, cfo, max_frames, C.byref(m))
+        if rc < 0:
+            raise RuntimeError("mi_acq_mib: " + last_error())
+        return m if rc == 1 else None
+
+    def close(self):
+        if self.h:
+            lib().mi_acq_destroy(self.h)
             self.h = None
 
     def __del__(self):

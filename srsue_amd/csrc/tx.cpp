@@ -12,6 +12,7 @@
 
 #include "dl_common.h"
 #include "mi_dl.h"
+#include "pbch.h"
 #include "tables.h"
 #include "sync.h"
 
@@ -298,6 +299,91 @@ extern "C" int mi_tx_sync(uint32_t cell_id, uint32_t nof_prb, uint32_t sf_idx, f
     }
   }
   return 1;
+}
+
+// PBCH (36.211 6.6, 36.212 5.3.1) of one radio frame: the quarter `phase` of the BCH TTI's 1920 bits, added to
+// a subframe-0 IQ buffer through the OFDM modulation of mi_tx_subframe (which leaves these REs empty).
+// CRC16 with the port mask -> tail-biting code -> rate matching -> scrambling (c_init = N_ID) -> QPSK ->
+// single port / SFBC -> flat per-port channel
+extern "C" int mi_tx_pbch(uint32_t cell_id, uint32_t nof_prb, uint32_t nof_ports, const uint8_t bch_payload[24],
+                          uint32_t phase, const float* h_re_im, float* iq) {
+  const int Ni = mi::symbol_sz(nof_prb);
+  if (Ni < 0 || nof_prb < 6 || !iq || !bch_payload || cell_id > 503 || phase > 3 || nof_ports < 1 || nof_ports > 2) {
+    mi::set_error("mi_tx_pbch: arguments");
+    return -1;
+  }
+  constexpr uint32_t A = mi::PBCH_A, D = mi::PBCH_D, E = mi::PBCH_E, NRE = mi::PBCH_RE;
+  const int N = Ni;
+  uint8_t c[D], d[3 * D], e[E], cs[E + 32];
+  uint32_t reg = 0;
+  for (uint32_t i = 0; i < A; i++) {
+    c[i] = bch_payload[i] & 1u;
+    const uint32_t fb = ((reg >> 15) ^ c[i]) & 1u;
+    reg = ((reg << 1) & 0xFFFFu) ^ (fb ? 0x1021u : 0u);
+  }
+  reg ^= nof_ports == 1 ? 0x0000u : 0xFFFFu;   // 36.212 Table 5.3.1.1-1
+  for (uint32_t i = 0; i < 16; i++) c[A + i] = (reg >> (15 - i)) & 1u;
+  static const uint32_t G[3] = {0133, 0171, 0165};   // bit 6 <-> c_k, bit 0 <-> c_{k-6}
+  for (uint32_t k = 0; k < D; k++) {
+    uint32_t sr = 0;
+    for (uint32_t j = 0; j <= 6; j++) sr |= (uint32_t)c[(k + D - j) % D] << (6 - j);
+    for (int i = 0; i < 3; i++) d[i * D + k] = (uint8_t)(__builtin_popcount(sr & G[i]) & 1);
+  }
+  std::vector<uint32_t> rank;
+  mi::conv_rank_table(D, rank);
+  uint32_t at_rank[3 * D];
+  for (uint32_t p = 0; p < 3 * D; p++) at_rank[rank[p]] = p;
+  for (uint32_t k = 0; k < E; k++) e[k] = d[at_rank[k % (3 * D)]];
+  mi::gold_bits(cell_id, E, cs);
+  uint32_t re[NRE];
+  mi::pbch_re_list(cell_id, nof_prb, re);
+  const uint32_t W = 12 * nof_prb;
+  // the four PBCH symbols' grids per port: [port][4][W]
+  std::vector<double> grid((size_t)nof_ports * 4 * W * 2, 0.0);
+  auto at = [&](uint32_t p, uint32_t idx) -> double* { return &grid[((size_t)p * 4 * W + (idx - 7 * W)) * 2]; };
+  const double a = 0.70710678118654752440, s2 = a;
+  auto sym = [&](uint32_t i, double* xr, double* xi) {
+    const uint32_t b = mi::PBCH_BITS * phase + 2 * i;
+    *xr = (1 - 2 * (int)(e[b] ^ cs[b])) * a;
+    *xi = (1 - 2 * (int)(e[b + 1] ^ cs[b + 1])) * a;
+  };
+  for (uint32_t i = 0; i < NRE; i += nof_ports) {
+    double xr, xi;
+    sym(i, &xr, &xi);
+    if (nof_ports == 1) {
+      double* y = at(0, re[i]); y[0] = xr; y[1] = xi;
+    } else {
+      double yr, yi;
+      sym(i + 1, &yr, &yi);
+      double* y = at(0, re[i]); y[0] = s2 * xr; y[1] = s2 * xi;
+      y = at(1, re[i]); y[0] = -s2 * yr; y[1] = s2 * yi;
+      y = at(0, re[i + 1]); y[0] = s2 * yr; y[1] = s2 * yi;
+      y = at(1, re[i + 1]); y[0] = s2 * xr; y[1] = -s2 * xi;
+    }
+  }
+  std::vector<double> X(2 * N);
+  const double nrm = 1.0 / sqrt((double)N);
+  for (uint32_t p = 0; p < nof_ports; p++) {
+    const double hr = h_re_im ? h_re_im[2 * p] : (p == 0 ? 1.0 : 0.0), hi = h_re_im ? h_re_im[2 * p + 1] : 0.0;
+    for (int l = 7; l <= 10; l++) {
+      std::fill(X.begin(), X.end(), 0.0);
+      for (uint32_t k = 0; k < W; k++) {
+        const int bin = mi::sc_bin((int)k, (int)W, N);
+        const double* y = at(p, (uint32_t)l * W + k);
+        X[2 * bin] = y[0];
+        X[2 * bin + 1] = y[1];
+      }
+      mi::idft(X, N);
+      const int cp = mi::cp_len(N, l % 7), s0 = mi::symbol_offset(N, l) - cp;
+      for (int n = 0; n < cp + N; n++) {
+        const int src = n < cp ? N - cp + n : n - cp;
+        const double sr = X[2 * src] * nrm, si = X[2 * src + 1] * nrm;
+        iq[2 * (s0 + n)] += (float)(hr * sr - hi * si);
+        iq[2 * (s0 + n) + 1] += (float)(hr * si + hi * sr);
+      }
+    }
+  }
+  return 0;
 }
 
 extern "C" int mi_sf_len(uint32_t nof_prb) {
