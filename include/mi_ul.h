@@ -16,6 +16,14 @@
  * sequence, RI (1 or 2 bits) in the interleaver columns next to the HARQ-ACK ones (rate matching of the
  * data around both), HARQ-ACK (1 or 2 bits) puncturing the data next to the DMRS.
  * Normalisation: unit average power per used subcarrier (1/sqrt(M) DFT, 1/sqrt(N) IDFT).
+ *
+ * PUCCH (36.211 5.4 / 5.5.2.2, srsue_amd/csrc/pucch.hip): formats 1/1a/1b and 2/2a/2b, the second half of this
+ * header.  mi_pucch_resource derives the resource (PRBs, sequence group, n', orthogonal cover and the cyclic
+ * shift of every symbol), mi_pucch_select picks format and resource for a UCI combination (36.213 10.1, FDD),
+ * mi_pucch_batch_* plans N transmissions once and encodes them per call from one device word of UCI each
+ * into device-resident SC-FDMA IQ with the layout and normalisation of the PUSCH batch.  Limits: normal CP,
+ * FDD, CQI payloads of A <= 11 bits (the (20, A) code's columns 0..10), no SPS resources, no format 3; SRS,
+ * PRACH and UL power control are not implemented.
  */
 #ifndef MI_UL_H
 #define MI_UL_H
@@ -77,6 +85,48 @@ double mi_ul_batch_algo_bytes(const mi_ul_batch_t *b);
  * Returns the lowest PRB of the mapped set, or -1 if the set is not L contiguous PRBs inside the band. */
 int mi_ul_hop_type2(uint32_t nof_prb, uint32_t n_ho, uint32_t n_sb, int intra, uint32_t cell_id, uint32_t n_vrb,
                     uint32_t L, uint32_t ns, uint32_t current_tx_nb);
+
+/* ---- PUCCH formats 1/1a/1b and 2/2a/2b (36.211 5.4, 5.5.2.2; normal CP, FDD) ------------------------- */
+enum { MI_PUCCH_1 = 0, MI_PUCCH_1A, MI_PUCCH_1B, MI_PUCCH_2, MI_PUCCH_2A, MI_PUCCH_2B };
+typedef struct {
+  uint32_t cell_id, nof_prb, sf_idx, rnti;
+  uint32_t format;                      /* MI_PUCCH_* */
+  uint32_t n_pucch;                     /* n_pucch^(1) for 1/1a/1b, n_pucch^(2) for 2/2a/2b */
+  uint32_t delta_shift, N_cs, n_rb_2;   /* deltaPUCCH-Shift 1..3, nCS-AN 0..7, nRB-CQI */
+  uint32_t group_hopping;               /* sequence-group hopping on/off (v = 0 always: M_sc = 12) */
+  uint32_t shortened;                   /* formats 1/1a/1b: last symbol of slot 1 not sent */
+  uint32_t cqi_len;                     /* formats 2/2a/2b: A = 1..11 */
+} mi_pucch_cfg_t;
+typedef struct {                        /* everything the kernel needs, and what the CPU tests compare */
+  uint32_t n_prb[2];                    /* PRB of slots 0 / 1 */
+  uint32_t u[2];                        /* base-sequence group per slot */
+  uint32_t n_prime[2], n_oc[2];         /* n'(ns); orthogonal-cover index (formats 1x, 0 for 2x) */
+  uint32_t n_cs[2][7];                  /* cyclic shift per (slot, symbol): alpha = 2 pi n_cs / 12 */
+} mi_pucch_res_t;
+/* host only (no device needed).  Every field of *c is checked first: 0, or -1 + mi_last_error with *r untouched */
+int mi_pucch_resource(const mi_pucch_cfg_t *c, mi_pucch_res_t *r);
+/* the same for n configurations: r[i] from c[i], stopping at the first one rejected; returns how many were planned */
+uint32_t mi_pucch_resource_n(const mi_pucch_cfg_t *c, uint32_t n, mi_pucch_res_t *r);
+/* 36.213 10.1 (FDD): which format on which resource for this UCI.  ack_len 0..2 HARQ-ACK bits, sr = positive
+ * scheduling request, cqi_len = CQI bits to report (simul_cqi_ack_dropped = 1: simultaneousAckNackAndCQI is off,
+ * a CQI that meets a HARQ-ACK is dropped and the HARQ-ACK goes alone).  A CQI that meets a positive SR is
+ * dropped.  Returns the format and writes the resource to *n_pucch; -1 = nothing to send. */
+int mi_pucch_select(uint32_t ack_len, int sr, uint32_t cqi_len, int simul_cqi_ack_dropped, uint32_t n_cce,
+                    uint32_t N_pucch_1, uint32_t n_pucch_2, uint32_t n_pucch_sr, uint32_t *n_pucch);
+
+/* UCI word of one transmission: bits 0-1 HARQ-ACK (bit 0 = first), bits 8-18 CQI bits o_0 .. o_10 */
+#define MI_PUCCH_UCI(ack, cqi) (((uint32_t)(ack) & 3u) | (((uint32_t)(cqi) & 0x7FFu) << 8))
+typedef struct mi_pucch_batch mi_pucch_batch_t;
+mi_pucch_batch_t *mi_pucch_batch_create(const mi_pucch_cfg_t *cfgs, uint32_t n, uint32_t flags);
+void   mi_pucch_batch_destroy(mi_pucch_batch_t *b);
+/* output layout: subframe i (15 N cf32 samples) at cf32 offset mi_pucch_batch_iq_offset(b, i) */
+size_t mi_pucch_batch_iq_offset(const mi_pucch_batch_t *b, uint32_t i);
+size_t mi_pucch_batch_iq_samples(const mi_pucch_batch_t *b);
+/* enqueue on `stream` (hipStream_t, NULL = default): d_uci (n device uint32 words) -> d_iq; the plan is reused
+ * across runs, every sample of every subframe is written */
+int    mi_pucch_batch_run(mi_pucch_batch_t *b, const uint32_t *d_uci, void *d_iq, void *stream);
+/* parity hook: the planned resource of transmission i */
+int    mi_pucch_batch_resource(const mi_pucch_batch_t *b, uint32_t i, mi_pucch_res_t *r);
 
 #ifdef __cplusplus
 }

@@ -286,9 +286,10 @@ SRSLTE_API void srslte_vec_free(void *ptr);
  * CQI (uci_cqi / uci_cqi_len, up to 64 bits: the (32, O) block code up to 11 bits, CRC8 + tail-biting
  * convolutional code above) and RI (uci_ri / uci_ri_len, 1 or 2 bits).  Limits: PUSCH hopping type 1 only (36.213 8.4.1: DCI format 0 hopping
  * bits through srslte_dci_msg_to_ul_grant's n_rb_ho, intra- or inter-subframe mode from set_cfg's hopping
- * configuration; type 2 returns SRSLTE_ERROR), L_prb >= 3; PUCCH, SRS and UL
- * power control stay in srsLTE.  set_cfg uses the DMRS and hopping configurations, the others are
- * accepted.  set_normalization(true) scales by nof_prb / (15 sqrt(L_prb)) (srsLTE's factor as recorded
+ * configuration; type 2 returns SRSLTE_ERROR), L_prb >= 3; SRS and UL
+ * power control stay in srsLTE.  PUCCH formats 1/1a/1b and 2/2a/2b are available under the library's own name,
+ * mi_ue_ul_pucch_encode below (and batched as mi_pucch_* in mi_ul.h).  set_cfg uses the DMRS, hopping, UCI and
+ * PUCCH configurations (pucch_cfg, pucch_sched), the others are accepted.  set_normalization(true) scales by nof_prb / (15 sqrt(L_prb)) (srsLTE's factor as recorded
  * in DESIGN.md, unverified: srsLTE is not in the container); set_cfo(cfo) shifts the output by cfo
  * subcarrier spacings when set_cfo_enable(true). */
 #define SRSLTE_CQI_MAX_BITS 64
@@ -331,7 +332,7 @@ typedef struct SRSLTE_API {           /* accepted by set_cfg, used by srsLTE's S
   bool configured;
   uint32_t subframe_config, bw_cfg, I_srs, B, b_hop, n_rrc, k_tc, n_srs;
 } srslte_refsignal_srs_cfg_t;
-typedef struct SRSLTE_API {           /* accepted by set_cfg (PUCCH: out of scope) */
+typedef struct SRSLTE_API {           /* kept by set_cfg for mi_ue_ul_pucch_encode */
   uint32_t delta_pucch_shift, N_cs, n_rb_2;
   bool srs_configured;
   uint32_t srs_cs_subf_cfg;
@@ -373,7 +374,7 @@ typedef struct SRSLTE_API {
   uint32_t current_tx_nb;
 } srslte_pusch_cfg_t;
 struct mi_ue_ul_ctx;
-typedef struct SRSLTE_API {         /* PUCCH state srsUE reads (phch_worker.cc:628); PUCCH itself is out of scope */
+typedef struct SRSLTE_API {         /* PUCCH state srsUE reads (phch_worker.cc:628), set by mi_ue_ul_pucch_encode */
   bool shortened;
 } srslte_pucch_t;
 typedef struct SRSLTE_API {         /* owned by value per phch_worker (phch_worker.h:116) */
@@ -406,6 +407,20 @@ SRSLTE_API int srslte_ue_ul_cfg_grant(srslte_ue_ul_t *q, srslte_ra_ul_grant_t *g
 SRSLTE_API int srslte_ue_ul_pusch_encode_rnti_softbuffer(srslte_ue_ul_t *q, uint8_t *data, srslte_uci_data_t uci_data,
                                                          srslte_softbuffer_tx_t *softbuffer, uint16_t rnti,
                                                          cf_t *output_signal);
+/* PUCCH (36.211 5.4, srsue_amd/csrc/pucch.hip): the arguments and return convention of the PUCCH encode call of
+ * srsUE's worker (phch_worker.cc:610), under the library's own name.  Format and resource follow 36.213 10.1 (FDD)
+ * from uci_data: HARQ-ACK (1 or 2 bits) on n_cce + N_pucch_1 as format 1a / 1b, on n_pucch_sr with a positive
+ * scheduling request (format 1 for the request alone), periodic CQI on n_pucch_2 as format 2 / 2a / 2b (dropped when
+ * it meets a positive request); pucch_cfg, pucch_sched and dmrs_cfg.group_hopping_en come from set_cfg.  Formats
+ * 1/1a/1b are shortened in a cell-specific SRS subframe when srs_configured and srs_simul_ack are set.  Sets
+ * q->last_pucch_format (0..5 = 1, 1a, 1b, 2, 2a, 2b) and q->pucch.shortened, encodes on the instance's stream and
+ * copies the subframe (SRSLTE_SF_LEN_PRB samples) to output_signal; the PUSCH grant and softbuffers are untouched.
+ * set_normalization(true) scales by nof_prb / 15 (the PUSCH factor with L_prb = 1, unverified against srsLTE like
+ * it); set_cfo applies as for PUSCH.  Limits: normal CP, FDD, CQI of at most 11 bits, no SPS resources
+ * (n_pucch_1[] unused), no format 3.  Returns SRSLTE_ERROR (mi_last_error) for an invalid configuration or when
+ * uci_data holds nothing to send. */
+SRSLTE_API int mi_ue_ul_pucch_encode(srslte_ue_ul_t *q, srslte_uci_data_t uci_data, uint32_t pdcch_n_cce,
+                                     uint32_t tti, cf_t *output_signal);
 SRSLTE_API int srslte_softbuffer_tx_init(srslte_softbuffer_tx_t *q, uint32_t nof_prb);
 SRSLTE_API void srslte_softbuffer_tx_reset(srslte_softbuffer_tx_t *q);
 SRSLTE_API void srslte_softbuffer_tx_free(srslte_softbuffer_tx_t *q);
@@ -497,10 +512,10 @@ SRSLTE_API int srslte_refsignal_srs_send_cs(uint32_t subframe_config, uint32_t s
 SRSLTE_API int srslte_refsignal_srs_send_ue(uint32_t I_srs, uint32_t tti);
 SRSLTE_API void srslte_ra_pusch_fprint(FILE *f, srslte_ra_ul_dci_t *q, uint32_t nof_prb);
 
-/* ---- OUT OF SCOPE (SURVEY.md 8 / DESIGN.md 9): PUCCH, SRS, UL power control and PRACH are not on the
- * DL decode path.  They are declared so srsUE compiles against this header unchanged; this library does
- * not implement them: an integration links srsLTE's own modules rebuilt against this header, or stubs
- * (INTEGRATION.md). -------- */
+/* ---- OUT OF SCOPE (SURVEY.md 8 / DESIGN.md 9): SRS, UL power control and PRACH are not implemented, and
+ * no srslte_* PUCCH name is exported.  They are declared so srsUE compiles against this header unchanged: an
+ * integration links srsLTE's own modules rebuilt against this header, or stubs.  PUCCH
+ * itself exists under the library's own names: mi_ue_ul_pucch_encode above, mi_pucch_* in mi_ul.h. -------- */
 SRSLTE_API void srslte_ue_ul_pregen_signals(srslte_ue_ul_t *q);
 SRSLTE_API int srslte_ue_ul_pucch_encode(srslte_ue_ul_t *q, srslte_uci_data_t uci_data, uint32_t pdcch_n_cce,
                                          uint32_t tti, cf_t *output_signal);

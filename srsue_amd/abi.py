@@ -173,6 +173,15 @@ def lib():
             "mi_ul_batch_stage_ms": (C.c_int, [vp, vp, vp]),
             "mi_ul_batch_profile_reset": (None, [vp]),
             "mi_ul_batch_algo_bytes": (C.c_double, [vp]),
+            "mi_pucch_resource": (C.c_int, [vp, vp]),
+            "mi_pucch_resource_n": (u32, [vp, u32, vp]),
+            "mi_pucch_select": (C.c_int, [u32, C.c_int, u32, C.c_int, u32, u32, u32, u32, vp]),
+            "mi_pucch_batch_create": (vp, [vp, u32, u32]),
+            "mi_pucch_batch_destroy": (None, [vp]),
+            "mi_pucch_batch_iq_offset": (sz, [vp, u32]),
+            "mi_pucch_batch_iq_samples": (sz, [vp]),
+            "mi_pucch_batch_run": (C.c_int, [vp, vp, vp, vp]),
+            "mi_pucch_batch_resource": (C.c_int, [vp, u32, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -967,3 +976,102 @@ class UlBatch:
 
     def algo_bytes(self):
         return lib().mi_ul_batch_algo_bytes(self.h)
+
+
+# ---- PUCCH formats 1/1a/1b, 2/2a/2b (include/mi_ul.h) -----------------------------------------------
+PUCCH_1, PUCCH_1A, PUCCH_1B, PUCCH_2, PUCCH_2A, PUCCH_2B = range(6)
+PUCCH_CFG_FIELDS = ("cell_id", "nof_prb", "sf_idx", "rnti", "format", "n_pucch", "delta_shift", "N_cs", "n_rb_2",
+                    "group_hopping", "shortened", "cqi_len")
+
+
+class PucchCfg(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in PUCCH_CFG_FIELDS]
+
+
+class PucchRes(C.Structure):
+    _fields_ = [("n_prb", C.c_uint32 * 2), ("u", C.c_uint32 * 2), ("n_prime", C.c_uint32 * 2),
+                ("n_oc", C.c_uint32 * 2), ("n_cs", (C.c_uint32 * 7) * 2)]
+
+
+# the same layouts as numpy records, for mi_pucch_resource_n over arrays of configurations
+PUCCH_CFG_DTYPE = np.dtype([(n, np.uint32) for n in PUCCH_CFG_FIELDS])
+PUCCH_RES_DTYPE = np.dtype([("n_prb", np.uint32, 2), ("u", np.uint32, 2), ("n_prime", np.uint32, 2),
+                            ("n_oc", np.uint32, 2), ("n_cs", np.uint32, (2, 7))])
+
+
+def pucch_cfg(cell_id=1, nof_prb=6, sf_idx=0, rnti=0x46, format=PUCCH_1A, n_pucch=0, delta_shift=1, N_cs=0, n_rb_2=0,
+              group_hopping=0, shortened=0, cqi_len=0):
+    return PucchCfg(cell_id, nof_prb, sf_idx, rnti, format, n_pucch, delta_shift, N_cs, n_rb_2, group_hopping,
+                    shortened, cqi_len)
+
+
+def pucch_uci(ack=0, cqi=()):
+    """the UCI word of one transmission: HARQ-ACK bits 0-1 (bit 0 = first), CQI bits o_0.. at bits 8.."""
+    w = ack & 3
+    for k, b in enumerate(cqi):
+        w |= (int(b) & 1) << (8 + k)
+    return w
+
+
+def pucch_resource(cfg):
+    """mi_pucch_resource: the planned PucchRes; raises on a rejected configuration"""
+    r = PucchRes()
+    if lib().mi_pucch_resource(C.byref(cfg), C.byref(r)):
+        raise RuntimeError("mi_pucch_resource: " + last_error())
+    return r
+
+
+def pucch_resource_n(cfgs):
+    """mi_pucch_resource_n over a PUCCH_CFG_DTYPE array: (records planned before the first rejection, their count)"""
+    cfgs = np.ascontiguousarray(cfgs, PUCCH_CFG_DTYPE)
+    out = np.zeros(len(cfgs), PUCCH_RES_DTYPE)
+    n = lib().mi_pucch_resource_n(cfgs.ctypes.data, len(cfgs), out.ctypes.data)
+    return out[:n], n
+
+
+def pucch_select(ack_len=0, sr=False, cqi_len=0, simul_cqi_ack_dropped=False, n_cce=0, N_pucch_1=0, n_pucch_2=0,
+                 n_pucch_sr=0):
+    """mi_pucch_select: (format, n_pucch), or None when there is nothing to send"""
+    n = C.c_uint32(0)
+    f = lib().mi_pucch_select(ack_len, int(sr), cqi_len, int(simul_cqi_ack_dropped), n_cce, N_pucch_1, n_pucch_2,
+                              n_pucch_sr, C.byref(n))
+    return None if f < 0 else (f, n.value)
+
+
+class PucchBatch:
+    """Owns one mi_pucch_batch_t: N PUCCH transmissions planned once; run() encodes them from device UCI words."""
+
+    def __init__(self, cfgs):
+        self.cfgs = list(cfgs)
+        self._arr = (PucchCfg * len(self.cfgs))(*self.cfgs)
+        self.h = lib().mi_pucch_batch_create(C.cast(self._arr, C.c_void_p), len(self.cfgs), 0)
+        if not self.h:
+            raise RuntimeError("mi_pucch_batch_create: " + last_error())
+
+    def close(self):
+        if self.h:
+            lib().mi_pucch_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def iq_samples(self):
+        return lib().mi_pucch_batch_iq_samples(self.h)
+
+    def iq_offset(self, i):
+        return lib().mi_pucch_batch_iq_offset(self.h, i)
+
+    def run(self, d_uci_ptr, d_iq_ptr, stream_ptr=None):
+        if lib().mi_pucch_batch_run(self.h, C.c_void_p(d_uci_ptr), C.c_void_p(d_iq_ptr), C.c_void_p(stream_ptr or 0)):
+            raise RuntimeError("mi_pucch_batch_run: " + last_error())
+
+    def resource(self, i):
+        r = PucchRes()
+        if lib().mi_pucch_batch_resource(self.h, i, C.byref(r)):
+            raise RuntimeError("mi_pucch_batch_resource: " + last_error())
+        return r

@@ -5,6 +5,7 @@
 // UlEngine planned for the current grant (cfg_grant), a device payload buffer and a device subframe.
 // A retransmission (rv > 0) re-encodes the TB kept in the HARQ softbuffer: the circular buffer is a
 // deterministic function of the TB, so this equals srsLTE's reuse of its stored coded bits.
+// mi_ue_ul_pucch_encode (PUCCH, pucch.hip) shares the instance's stream and output staging and nothing else.
 #include <time.h>
 #include <math.h>
 #include <stdlib.h>
@@ -12,6 +13,7 @@
 
 #include "../../include/srslte/srslte.h"
 #include "tables.h"
+#include "pucch_engine.h"
 #include "ul_engine.h"
 #include "../../include/mi_ul.h"
 
@@ -24,6 +26,13 @@ struct mi_ue_ul_ctx {
   cf_t* h_iq = nullptr;
   mi_ul_cfg_t cfg{};
   bool planned = false;
+  // PUCCH (mi_ue_ul_pucch_encode): its own plan and tables, so a PUCCH subframe leaves the PUSCH plan above as
+  // it was; set_cfg's PUCCH configuration; one page-locked UCI word and its device copy
+  mi::PucchEngine pucch;
+  srslte_pucch_cfg_t pucch_cfg{};
+  srslte_pucch_sched_t pucch_sched{};
+  mi::DevBuf d_uci;
+  uint32_t* h_uci = nullptr;
   // per-phase host-clock breakdown of pusch_encode (MI_UE_UL_PROF=1: the stream is synchronised at every
   // mark so GPU work is attributed to its phase; printed to stderr when the instance is freed):
   // 0 payload H2D, 1 plan, 2 table upload, 3 kernels, 4 IQ D2H + copy out
@@ -56,6 +65,7 @@ struct mi_ue_ul_ctx {
     if (st) (void)hipStreamSynchronize(st);
     if (h_pay) (void)hipHostFree(h_pay);
     if (h_iq) (void)hipHostFree(h_iq);
+    if (h_uci) (void)hipHostFree(h_uci);
     if (st) (void)hipStreamDestroy(st);
   }
 };
@@ -150,7 +160,8 @@ int srslte_ue_ul_init(srslte_ue_ul_t* q, srslte_cell_t cell) {
   c->eng.packed = true;
   const size_t iq_bytes = (size_t)15 * mi::symbol_sz(cell.nof_prb) * 8;
   if (!mi::hip_ok(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking), "stream") || !c->d_pay.ensure(TX_MAX_BYTES) ||
-      !c->d_iq.ensure(iq_bytes) ||
+      !c->d_iq.ensure(iq_bytes) || !c->d_uci.ensure(sizeof(uint32_t)) ||
+      !mi::hip_ok(hipHostMalloc(reinterpret_cast<void**>(&c->h_uci), sizeof(uint32_t), hipHostMallocDefault), "pinned") ||
       !mi::hip_ok(hipHostMalloc(reinterpret_cast<void**>(&c->h_pay), TX_MAX_BYTES, hipHostMallocDefault), "pinned") ||
       !mi::hip_ok(hipHostMalloc(reinterpret_cast<void**>(&c->h_iq), iq_bytes, hipHostMallocDefault), "pinned")) {
     delete c;   // the destructor destroys the stream
@@ -180,9 +191,11 @@ void srslte_ue_ul_set_cfo(srslte_ue_ul_t* q, float cur_cfo) {
 }
 
 void srslte_ue_ul_set_cfg(srslte_ue_ul_t* q, srslte_refsignal_dmrs_pusch_cfg_t* dmrs_cfg, srslte_refsignal_srs_cfg_t*,
-                          srslte_pucch_cfg_t*, srslte_pucch_sched_t*, srslte_uci_cfg_t* uci_cfg,
+                          srslte_pucch_cfg_t* pucch_cfg, srslte_pucch_sched_t* pucch_sched, srslte_uci_cfg_t* uci_cfg,
                           srslte_pusch_hopping_cfg_t* hopping_cfg, srslte_ue_ul_powerctrl_t*) {
   if (!q) return;
+  if (q->ctx && pucch_cfg) q->ctx->pucch_cfg = *pucch_cfg;
+  if (q->ctx && pucch_sched) q->ctx->pucch_sched = *pucch_sched;
   if (dmrs_cfg) q->dmrs_cfg = *dmrs_cfg;
   if (hopping_cfg) q->hopping_cfg = *hopping_cfg;
   if (uci_cfg) q->uci_cfg = *uci_cfg;
@@ -311,6 +324,54 @@ int srslte_ue_ul_pusch_encode_rnti_softbuffer(srslte_ue_ul_t* q, uint8_t* data, 
     return SRSLTE_ERROR;
   memcpy(output_signal, c->h_iq, n * 8);
   c->prof.mark(4, c->st);
+  return SRSLTE_SUCCESS;
+}
+
+// PUCCH (36.211 5.4): srsUE's PUCCH encode call (phch_worker.cc:610) under the library's own name.  Format and
+// resource by 36.213 10.1 (mi_pucch_select; srsUE has already dropped a CQI that may not go with a HARQ-ACK),
+// planned and encoded on the instance's stream by pucch.hip, the subframe copied to output_signal.
+int mi_ue_ul_pucch_encode(srslte_ue_ul_t* q, srslte_uci_data_t uci, uint32_t pdcch_n_cce, uint32_t tti,
+                          cf_t* output_signal) {
+  if (!q || !q->ctx || !output_signal) return SRSLTE_ERROR_INVALID_INPUTS;
+  mi_ue_ul_ctx* c = q->ctx;
+  if (uci.uci_ack_len > 2) { mi::set_error("PUCCH: up to 2 HARQ-ACK bits"); return SRSLTE_ERROR; }
+  uint32_t n_pucch = 0;
+  const int format = mi_pucch_select(uci.uci_ack_len, uci.scheduling_request ? 1 : 0, uci.uci_cqi_len, 0, pdcch_n_cce,
+                                     c->pucch_sched.N_pucch_1, c->pucch_sched.n_pucch_2, c->pucch_sched.n_pucch_sr,
+                                     &n_pucch);
+  if (format < 0) { mi::set_error("PUCCH: no UCI to send"); return SRSLTE_ERROR; }
+  mi_pucch_cfg_t p{};
+  p.cell_id = q->cell.id;
+  p.nof_prb = q->cell.nof_prb;
+  p.sf_idx = tti % 10;
+  p.rnti = q->current_rnti;
+  p.format = (uint32_t)format;
+  p.n_pucch = n_pucch;
+  p.delta_shift = c->pucch_cfg.delta_pucch_shift;
+  p.N_cs = c->pucch_cfg.N_cs;
+  p.n_rb_2 = c->pucch_cfg.n_rb_2;
+  p.group_hopping = q->dmrs_cfg.group_hopping_en;
+  // formats 1/1a/1b leave the last symbol to the SRS in a cell-specific SRS subframe (36.213 8.2) when
+  // ackNackSRS-SimultaneousTransmission is on
+  p.shortened = format <= MI_PUCCH_1B && c->pucch_cfg.srs_configured && c->pucch_cfg.srs_simul_ack &&
+                srslte_refsignal_srs_send_cs(c->pucch_cfg.srs_cs_subf_cfg, tti % 10) == 1;
+  p.cqi_len = format >= MI_PUCCH_2 ? uci.uci_cqi_len : 0;
+  if (c->pucch.plan.build(&p, 1)) return SRSLTE_ERROR;   // every field checked: nothing is launched on an error
+  MiPucchTx& t = c->pucch.plan.txs[0];
+  if (q->normalize_en) t.scale = (float)q->cell.nof_prb / 15.0f;   // the PUSCH factor with L_prb = 1
+  if (q->cfo_en) t.cfo = q->current_cfo;
+  uint32_t word = uci.uci_ack & 3u;
+  for (uint32_t k = 0; k < p.cqi_len; k++) word |= (uint32_t)(uci.uci_cqi[k] & 1u) << (8 + k);
+  *c->h_uci = word;   // the previous call's DMA out of h_uci ended with its stream sync
+  const size_t n = (size_t)15 * mi::symbol_sz(q->cell.nof_prb);
+  if (!mi::hip_ok(hipMemcpyAsync(c->d_uci.p, c->h_uci, sizeof(uint32_t), hipMemcpyHostToDevice, c->st), "H2D UCI") ||
+      c->pucch.upload(c->st) || c->pucch.run(c->d_uci.as<uint32_t>(), c->d_iq.p, c->st) ||
+      !mi::hip_ok(hipMemcpyAsync(c->h_iq, c->d_iq.p, n * 8, hipMemcpyDeviceToHost, c->st), "D2H IQ") ||
+      !mi::hip_ok(hipStreamSynchronize(c->st), "pucch sync"))
+    return SRSLTE_ERROR;
+  memcpy(output_signal, c->h_iq, n * 8);
+  q->last_pucch_format = (uint32_t)format;
+  q->pucch.shortened = p.shortened != 0;
   return SRSLTE_SUCCESS;
 }
 
