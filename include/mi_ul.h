@@ -22,8 +22,14 @@
  * shift of every symbol), mi_pucch_select picks format and resource for a UCI combination (36.213 10.1, FDD),
  * mi_pucch_batch_* plans N transmissions once and encodes them per call from one device word of UCI each
  * into device-resident SC-FDMA IQ with the layout and normalisation of the PUSCH batch.  Limits: normal CP,
- * FDD, CQI payloads of A <= 11 bits (the (20, A) code's columns 0..10), no SPS resources, no format 3; SRS,
- * PRACH and UL power control are not implemented.
+ * FDD, CQI payloads of A <= 11 bits (the (20, A) code's columns 0..10), no SPS resources, no format 3.
+ *
+ * PRACH (36.211 5.7, srsue_amd/csrc/prach.hip): the preamble of formats 0-3, the last part of this header.
+ * mi_prach_resource derives format, lengths, physical root, cyclic shift and frequency position of one preamble of
+ * a cell (unrestricted and restricted sets), mi_prach_send_tti is the timing of Table 5.7.1-2, mi_prach_batch_*
+ * plans N preambles once and generates them per call into device-resident IQ at the UL sample rate, with an optional
+ * frequency shift and scale per transmission.  Limits: FDD, formats 0-3 (no format 4), no power ramping.  SRS and
+ * UL power control are not implemented.
  */
 #ifndef MI_UL_H
 #define MI_UL_H
@@ -127,6 +133,52 @@ size_t mi_pucch_batch_iq_samples(const mi_pucch_batch_t *b);
 int    mi_pucch_batch_run(mi_pucch_batch_t *b, const uint32_t *d_uci, void *d_iq, void *stream);
 /* parity hook: the planned resource of transmission i */
 int    mi_pucch_batch_resource(const mi_pucch_batch_t *b, uint32_t i, mi_pucch_res_t *r);
+
+/* ---- PRACH preamble, formats 0-3 (36.211 5.7; FDD, N_ZC = 839) --------------------------------------- */
+typedef struct {
+  uint32_t nof_prb;          /* 6, 15, 25, 50, 75, 100 */
+  uint32_t config_idx;       /* prach-ConfigIndex 0..63 (30, 46, 60, 61, 62 are N/A) */
+  uint32_t root_seq_idx;     /* rootSequenceIndex (logical) 0..837 */
+  uint32_t zero_corr_zone;   /* zeroCorrelationZoneConfig 0..15 (0..14 when high_speed) */
+  uint32_t high_speed;       /* restricted set */
+  uint32_t freq_offset;      /* n_PRBoffset^RA, 0..nof_prb-6 */
+  uint32_t preamble_idx;     /* 0..63 */
+} mi_prach_cfg_t;
+typedef struct {                        /* everything the kernels need, and what the CPU tests compare */
+  uint32_t format, N_ifft, N_cp, N_seq, N_cs;   /* N_ifft = 12 srslte_symbol_sz(nof_prb); samples at the UL rate */
+  uint32_t u, C_v;                      /* physical root and cyclic shift of preamble_idx */
+  uint32_t first_bin;                   /* bin of X(0) in the N_ifft-point grid: (13 + 12 k0) mod N_ifft */
+  uint32_t n_roots;                     /* distinct roots the cell's 64 preambles use */
+} mi_prach_res_t;
+/* host only (no device needed).  Every field of *c is checked first: 0, or -1 + mi_last_error with *r untouched.  A
+ * restricted-set configuration whose 838 roots give fewer than 64 preambles is rejected. */
+int mi_prach_resource(const mi_prach_cfg_t *c, mi_prach_res_t *r);
+/* the same for n configurations: r[i] from c[i], stopping at the first one rejected; returns how many were planned */
+uint32_t mi_prach_resource_n(const mi_prach_cfg_t *c, uint32_t n, mi_prach_res_t *r);
+/* Table 5.7.2-4: the physical root u of a logical index, -1 if it is > 837 */
+int mi_prach_root(uint32_t logical_idx);
+/* Table 5.7.1-2 (FDD): the preamble format 0..3 of a prach-ConfigIndex, -1 for the N/A rows and indices > 63 */
+int mi_prach_format(uint32_t config_idx);
+/* 1 iff a preamble may start in subframe tti % 10 of frame tti / 10 under config_idx and allowed_subframe is -1 or
+ * that subframe (srsUE prach.cc:130); 0 for the N/A rows */
+int mi_prach_send_tti(uint32_t config_idx, uint32_t tti, int allowed_subframe);
+
+/* a workgroup owns one residue of the polyphase transform instead of up to 4 adjacent ones (A/B: DESIGN.md) */
+#define MI_PRACH_FLAG_SINGLE_RESIDUE 1u
+typedef struct mi_prach_batch mi_prach_batch_t;
+mi_prach_batch_t *mi_prach_batch_create(const mi_prach_cfg_t *cfgs, uint32_t n, uint32_t flags);
+void   mi_prach_batch_destroy(mi_prach_batch_t *b);
+/* output layout: transmission i (N_cp + N_seq cf32 samples, CP first) at cf32 offset mi_prach_batch_iq_offset(b, i) */
+size_t mi_prach_batch_iq_offset(const mi_prach_batch_t *b, uint32_t i);
+size_t mi_prach_batch_iq_samples(const mi_prach_batch_t *b);
+/* enqueue on `stream` (hipStream_t, NULL = default).  d_cfo: n device floats, the frequency shift of each
+ * transmission in subcarriers of 15 kHz (sample i, counted from the first CP sample, is multiplied by
+ * exp(j 2 pi cfo i / N_ul)), NULL = none; d_scale: n device floats, NULL = 1.  Normalisation: unit power per PRACH
+ * subcarrier (mean power 839 / N_ifft over the sequence).  The plan is reused across runs (one run of a batch at a
+ * time), every sample of every transmission is written */
+int    mi_prach_batch_run(mi_prach_batch_t *b, const float *d_cfo, const float *d_scale, void *d_iq, void *stream);
+/* parity hook: the planned resource of transmission i */
+int    mi_prach_batch_resource(const mi_prach_batch_t *b, uint32_t i, mi_prach_res_t *r);
 
 #ifdef __cplusplus
 }

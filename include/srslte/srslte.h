@@ -9,8 +9,9 @@
  * ue_dl.chest, ue_dl.pdcch, ue_dl.last_n_cce, ue_dl.last_location) are kept.
  *
  * Beyond the DL data path the header also carries the SURVEY.md 8f rows built on the GPU: DL control
- * (PDCCH/DCI, PHICH), the sync tracking subset and the UL PUSCH encoder.  Cell search / MIB, PUCCH,
- * SRS, PRACH, power control and the radio still come from srsLTE itself.
+ * (PDCCH/DCI, PHICH), the sync tracking subset and the UL PUSCH encoder.  Cell search / MIB, PUCCH and the PRACH
+ * preamble exist under the library's own mi_* names; SRS, power control and the radio still come from srsLTE
+ * itself.
  *
  * Conventions: 0 = SRSLTE_SUCCESS, -1 = SRSLTE_ERROR; srslte_pdsch_decode_rnti returns 0 iff
  * the TB CRC passes; payload bits are packed MSB first.
@@ -512,10 +513,11 @@ SRSLTE_API int srslte_refsignal_srs_send_cs(uint32_t subframe_config, uint32_t s
 SRSLTE_API int srslte_refsignal_srs_send_ue(uint32_t I_srs, uint32_t tti);
 SRSLTE_API void srslte_ra_pusch_fprint(FILE *f, srslte_ra_ul_dci_t *q, uint32_t nof_prb);
 
-/* ---- OUT OF SCOPE (SURVEY.md 8 / DESIGN.md 9): SRS, UL power control and PRACH are not implemented, and
- * no srslte_* PUCCH name is exported.  They are declared so srsUE compiles against this header unchanged: an
- * integration links srsLTE's own modules rebuilt against this header, or stubs.  PUCCH
- * itself exists under the library's own names: mi_ue_ul_pucch_encode above, mi_pucch_* in mi_ul.h. -------- */
+/* ---- OUT OF SCOPE (SURVEY.md 8 / DESIGN.md 9): SRS and UL power control are not implemented, and no srslte_*
+ * PUCCH, PRACH or CFO name is exported.  They are declared so srsUE compiles against this header unchanged: an
+ * integration links srsLTE's own modules rebuilt against this header, or stubs.  PUCCH and the
+ * PRACH preamble exist under the library's own names: mi_ue_ul_pucch_encode above and mi_pucch_* in mi_ul.h,
+ * mi_prach_init / _gen / _gen_cfo at the end of this header and mi_prach_* in mi_ul.h. -------- */
 SRSLTE_API void srslte_ue_ul_pregen_signals(srslte_ue_ul_t *q);
 SRSLTE_API int srslte_ue_ul_pucch_encode(srslte_ue_ul_t *q, srslte_uci_data_t uci_data, uint32_t pdcch_n_cce,
                                          uint32_t tti, cf_t *output_signal);
@@ -604,6 +606,25 @@ SRSLTE_API uint32_t srslte_N_ta_new(uint32_t N_ta_old, uint32_t ta);
 SRSLTE_API void srslte_dci_rar_grant_unpack(srslte_dci_rar_grant_t *rar, uint8_t grant[SRSLTE_RAR_GRANT_LEN]);
 SRSLTE_API float srslte_vec_avg_power_cf(cf_t *x, uint32_t len);
 SRSLTE_API void srslte_vec_sc_prod_cfc(cf_t *x, float h, cf_t *z, uint32_t len);
+
+/* ---- PRACH preamble (36.211 5.7, srsue_amd/csrc/prach.hip): the calls of srsUE's prach.cc under the library's own
+ * names, in srsLTE's argument order (prach.cc:77-98: init + 64 x gen; :130 send_tti, declared in mi_ul.h as
+ * mi_prach_send_tti; :152,168: CFO shift + scale).  FDD, preamble formats 0-3, unrestricted and restricted sets.
+ * mi_prach_init checks the whole configuration on the host (N_ifft_ul = srslte_symbol_sz(nof_prb); an invalid one
+ * returns SRSLTE_ERROR with mi_last_error and touches no device) and fills p->N_seq and p->N_cp.  The first
+ * mi_prach_gen of a freq_offset generates all 64 preambles of the cell in one launch and keeps them on the device:
+ * each gen then copies N_cp + N_seq samples to signal.  Normalisation: unit power per PRACH subcarrier, so the mean
+ * power of the sequence part is 839 / (12 N_ifft_ul).  mi_prach_gen_cfo generates preamble seq_index multiplied by
+ * scale exp(j 2 pi cfo i / N_ifft_ul) at sample i (cfo in subcarriers of 15 kHz, what srslte_cfo_correct(..,
+ * cfo / symbol_sz) and srslte_vec_sc_prod_cfc do on the CPU).  The power ramp and the radio gain steps of
+ * prach.cc:155-177 stay with the caller; format 4 / TDD is not implemented. */
+SRSLTE_API int mi_prach_init(srslte_prach_t *p, uint32_t N_ifft_ul, uint32_t preamble_format, uint32_t root_seq_index,
+                             bool high_speed_flag, uint32_t zero_corr_zone_config);
+SRSLTE_API int mi_prach_free(srslte_prach_t *p);
+SRSLTE_API uint32_t mi_prach_get_preamble_format(uint32_t config_idx);   /* 0..3; 0xFFFFFFFF for an N/A index */
+SRSLTE_API int mi_prach_gen(srslte_prach_t *p, uint32_t seq_index, uint32_t freq_offset, cf_t *signal);
+SRSLTE_API int mi_prach_gen_cfo(srslte_prach_t *p, uint32_t seq_index, uint32_t freq_offset, float cfo, float scale,
+                                cf_t *signal);
 
 #ifdef __cplusplus
 }

@@ -182,6 +182,17 @@ def lib():
             "mi_pucch_batch_iq_samples": (sz, [vp]),
             "mi_pucch_batch_run": (C.c_int, [vp, vp, vp, vp]),
             "mi_pucch_batch_resource": (C.c_int, [vp, u32, vp]),
+            "mi_prach_resource": (C.c_int, [vp, vp]),
+            "mi_prach_resource_n": (u32, [vp, u32, vp]),
+            "mi_prach_root": (C.c_int, [u32]),
+            "mi_prach_format": (C.c_int, [u32]),
+            "mi_prach_send_tti": (C.c_int, [u32, u32, C.c_int]),
+            "mi_prach_batch_create": (vp, [vp, u32, u32]),
+            "mi_prach_batch_destroy": (None, [vp]),
+            "mi_prach_batch_iq_offset": (sz, [vp, u32]),
+            "mi_prach_batch_iq_samples": (sz, [vp]),
+            "mi_prach_batch_run": (C.c_int, [vp, vp, vp, vp, vp]),
+            "mi_prach_batch_resource": (C.c_int, [vp, u32, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -1074,4 +1085,98 @@ class PucchBatch:
         r = PucchRes()
         if lib().mi_pucch_batch_resource(self.h, i, C.byref(r)):
             raise RuntimeError("mi_pucch_batch_resource: " + last_error())
+        return r
+
+
+# ---- PRACH preamble, formats 0-3 (include/mi_ul.h) --------------------------------------------------
+PRACH_FLAG_SINGLE_RESIDUE = 1
+PRACH_CFG_FIELDS = ("nof_prb", "config_idx", "root_seq_idx", "zero_corr_zone", "high_speed", "freq_offset",
+                    "preamble_idx")
+PRACH_RES_FIELDS = ("format", "N_ifft", "N_cp", "N_seq", "N_cs", "u", "C_v", "first_bin", "n_roots")
+
+
+class PrachCfg(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in PRACH_CFG_FIELDS]
+
+
+class PrachRes(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in PRACH_RES_FIELDS]
+
+
+# the same layouts as numpy records, for mi_prach_resource_n over arrays of configurations
+PRACH_CFG_DTYPE = np.dtype([(n, np.uint32) for n in PRACH_CFG_FIELDS])
+PRACH_RES_DTYPE = np.dtype([(n, np.uint32) for n in PRACH_RES_FIELDS])
+
+
+def prach_cfg(nof_prb=6, config_idx=0, root_seq_idx=0, zero_corr_zone=0, high_speed=0, freq_offset=0, preamble_idx=0):
+    return PrachCfg(nof_prb, config_idx, root_seq_idx, zero_corr_zone, high_speed, freq_offset, preamble_idx)
+
+
+def prach_resource(cfg):
+    """mi_prach_resource: the planned PrachRes; raises on a rejected configuration"""
+    r = PrachRes()
+    if lib().mi_prach_resource(C.byref(cfg), C.byref(r)):
+        raise RuntimeError("mi_prach_resource: " + last_error())
+    return r
+
+
+def prach_resource_n(cfgs):
+    """mi_prach_resource_n over a PRACH_CFG_DTYPE array: (records planned before the first rejection, their count)"""
+    cfgs = np.ascontiguousarray(cfgs, PRACH_CFG_DTYPE)
+    out = np.zeros(len(cfgs), PRACH_RES_DTYPE)
+    n = lib().mi_prach_resource_n(cfgs.ctypes.data, len(cfgs), out.ctypes.data)
+    return out[:n], n
+
+
+def prach_root(logical_idx):
+    """mi_prach_root: the physical root of a logical index (Table 5.7.2-4), -1 beyond 837"""
+    return lib().mi_prach_root(logical_idx)
+
+
+def prach_format(config_idx):
+    """mi_prach_format: 0..3, -1 for the N/A rows"""
+    return lib().mi_prach_format(config_idx)
+
+
+def prach_send_tti(config_idx, tti, allowed_subframe=-1):
+    return lib().mi_prach_send_tti(config_idx, tti, allowed_subframe)
+
+
+class PrachBatch:
+    """Owns one mi_prach_batch_t: N preambles planned once; run() generates them into device IQ."""
+
+    def __init__(self, cfgs, flags=0):
+        self.cfgs = list(cfgs)
+        self._arr = (PrachCfg * len(self.cfgs))(*self.cfgs)
+        self.h = lib().mi_prach_batch_create(C.cast(self._arr, C.c_void_p), len(self.cfgs), flags)
+        if not self.h:
+            raise RuntimeError("mi_prach_batch_create: " + last_error())
+
+    def close(self):
+        if self.h:
+            lib().mi_prach_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def iq_samples(self):
+        return lib().mi_prach_batch_iq_samples(self.h)
+
+    def iq_offset(self, i):
+        return lib().mi_prach_batch_iq_offset(self.h, i)
+
+    def run(self, d_iq_ptr, stream_ptr=None, d_cfo_ptr=None, d_scale_ptr=None):
+        if lib().mi_prach_batch_run(self.h, C.c_void_p(d_cfo_ptr or 0), C.c_void_p(d_scale_ptr or 0),
+                                    C.c_void_p(d_iq_ptr), C.c_void_p(stream_ptr or 0)):
+            raise RuntimeError("mi_prach_batch_run: " + last_error())
+
+    def resource(self, i):
+        r = PrachRes()
+        if lib().mi_prach_batch_resource(self.h, i, C.byref(r)):
+            raise RuntimeError("mi_prach_batch_resource: " + last_error())
         return r
