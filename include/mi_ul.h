@@ -28,8 +28,23 @@
  * mi_prach_resource derives format, lengths, physical root, cyclic shift and frequency position of one preamble of
  * a cell (unrestricted and restricted sets), mi_prach_send_tti is the timing of Table 5.7.1-2, mi_prach_batch_*
  * plans N preambles once and generates them per call into device-resident IQ at the UL sample rate, with an optional
- * frequency shift and scale per transmission.  Limits: FDD, formats 0-3 (no format 4), no power ramping.  SRS and
- * UL power control are not implemented.
+ * frequency shift and scale per transmission.  Limits: FDD, formats 0-3 (no format 4), no power ramping.
+ *
+ * SRS (36.211 5.5.3, srsue_amd/csrc/srs.hip): the periodic sounding reference signal.  mi_srs_resource derives the
+ * bandwidth, the frequency position (with frequency hopping), the base sequence and the cyclic shift of one
+ * transmission, mi_srs_batch_* plans N transmissions once and encodes them per call into device-resident SC-FDMA IQ
+ * with the layout and normalisation of the PUSCH batch: symbols 0..12 zero, the SRS in symbol 13.  Limits: FDD,
+ * normal CP, one antenna port, no aperiodic SRS.  PUSCH is not shortened in cell-specific SRS subframes.
+ *
+ * Open-loop UL power control (36.213 5.1): mi_ul_pusch_power, mi_ul_pucch_power, mi_ul_srs_power, host only, at the
+ * end of this header.  Limit: no TPC accumulation (f(i) = g(i) = 0).
+ *
+ * srsUE's calls (phch_worker.cc) and the per-TTI calls of srslte/srslte.h over this header:
+ *   srslte_ue_ul_srs_encode(&ue_ul, tti, signal)            :641 -> mi_ue_ul_srs_encode    (mi_srs_resource, srs.hip)
+ *   srslte_ue_ul_srs_power(&ue_ul, PL)                      :652 -> mi_ue_ul_srs_power     (mi_ul_srs_power)
+ *   srslte_ue_ul_pusch_power(&ue_ul, PL, p0_preamble)       :568 -> mi_ue_ul_pusch_power   (mi_ul_pusch_power)
+ *   srslte_ue_ul_pucch_power(&ue_ul, PL, format, n_cqi, n_harq) :622 -> mi_ue_ul_pucch_power (mi_ul_pucch_power)
+ * srsUE's own flow never sends the SRS together with PUSCH or PUCCH in one subframe.
  */
 #ifndef MI_UL_H
 #define MI_UL_H
@@ -179,6 +194,70 @@ size_t mi_prach_batch_iq_samples(const mi_prach_batch_t *b);
 int    mi_prach_batch_run(mi_prach_batch_t *b, const float *d_cfo, const float *d_scale, void *d_iq, void *stream);
 /* parity hook: the planned resource of transmission i */
 int    mi_prach_batch_resource(const mi_prach_batch_t *b, uint32_t i, mi_prach_res_t *r);
+
+/* ---- SRS, periodic (36.211 5.5.3, 36.213 8.2; FDD, normal CP, one antenna port) ------------------------ */
+typedef struct {
+  uint32_t cell_id, nof_prb, tti;       /* tti 0..10239: subframe tti % 10 of frame tti / 10 */
+  uint32_t bw_cfg;                      /* cell: srs-BandwidthConfig C_SRS 0..7 */
+  uint32_t B, b_hop, n_rrc, k_tc;       /* UE: srs-Bandwidth 0..3, srs-HoppingBandwidth 0..3, freqDomainPosition
+                                           0..23, transmissionComb 0/1 */
+  uint32_t n_srs, I_srs;                /* UE: cyclicShift 0..7, srs-ConfigIndex 0..636 (637.. reserved) */
+  uint32_t group_hopping, sequence_hopping, delta_ss;   /* the cell's UL reference-signal configuration */
+} mi_srs_cfg_t;
+typedef struct {                        /* everything the kernel needs, and what the CPU tests compare */
+  uint32_t m_srs, M_sc;                 /* m_SRS,B in PRBs, sequence length 6 m_srs */
+  uint32_t k0;                          /* first subcarrier, 0 .. 12 nof_prb - 1; the SRS occupies k0 + 2 k' */
+  uint32_t n_b[4];                      /* frequency position index per level b <= B (0 above B) */
+  uint32_t n_SRS, T_srs;                /* transmission counter floor(tti / T_SRS), periodicity in subframes */
+  uint32_t u, v;                        /* sequence group and base sequence number in slot 2 (tti % 10) + 1 */
+  uint32_t nzc, q;                      /* Zadoff-Chu length and root; nzc = 0: the tabulated M_sc = 24 sequence of
+                                           group q = u */
+  uint32_t n_cs;                        /* alpha = 2 pi n_cs / 8 */
+} mi_srs_res_t;
+/* host only (no device needed).  Every field of *c is checked first: 0, or -1 + mi_last_error with *r untouched.  A
+ * configuration whose m_SRS,0 exceeds nof_prb is rejected (6 PRB admits only C_SRS = 7). */
+int mi_srs_resource(const mi_srs_cfg_t *c, mi_srs_res_t *r);
+/* the same for n configurations: r[i] from c[i], stopping at the first one rejected; returns how many were planned */
+uint32_t mi_srs_resource_n(const mi_srs_cfg_t *c, uint32_t n, mi_srs_res_t *r);
+
+/* write only the N + CP samples of symbol 13 of every subframe and leave the rest as it was: the SRS laid over a
+ * shortened PUCCH subframe that mi_pucch_batch_run wrote before it on the same stream */
+#define MI_SRS_FLAG_LAST_SYMBOL_ONLY 1u
+typedef struct mi_srs_batch mi_srs_batch_t;
+mi_srs_batch_t *mi_srs_batch_create(const mi_srs_cfg_t *cfgs, uint32_t n, uint32_t flags);
+void   mi_srs_batch_destroy(mi_srs_batch_t *b);
+/* output layout: subframe i (15 N cf32 samples) at cf32 offset mi_srs_batch_iq_offset(b, i) */
+size_t mi_srs_batch_iq_offset(const mi_srs_batch_t *b, uint32_t i);
+size_t mi_srs_batch_iq_samples(const mi_srs_batch_t *b);
+/* enqueue on `stream` (hipStream_t, NULL = default).  d_cfo: n device floats, the frequency shift of each
+ * transmission in subcarriers (sample i of the subframe is multiplied by exp(j 2 pi cfo i / N)), NULL = none;
+ * d_scale: n device floats, NULL = 1.  Normalisation: unit power per occupied subcarrier.  The plan is reused across
+ * runs; every sample of every subframe is written (symbols 0..12 with zeros) unless MI_SRS_FLAG_LAST_SYMBOL_ONLY */
+int    mi_srs_batch_run(mi_srs_batch_t *b, const float *d_cfo, const float *d_scale, void *d_iq, void *stream);
+/* parity hook: the planned resource of transmission i */
+int    mi_srs_batch_resource(const mi_srs_batch_t *b, uint32_t i, mi_srs_res_t *r);
+
+/* ---- open-loop UL power control (36.213 5.1.1.1, 5.1.2.1, 5.1.3.1), host only --------------------------- */
+typedef struct {                        /* the fields of srslte_ue_ul_powerctrl_t, dB / dBm */
+  float p0_nominal_pusch, alpha, p0_nominal_pucch;
+  float delta_f_pucch[5];               /* deltaF-PUCCH of formats 1, 1b, 2, 2a, 2b (1a is the reference: 0) */
+  float delta_preamble_msg3, p0_ue_pusch;
+  uint32_t delta_mcs_based;             /* deltaMCS-Enabled: K_S = 1.25, else 0 */
+  uint32_t acc_enabled;                 /* stored, unused: the TPC accumulations f(i) = g(i) = 0 */
+  float p0_ue_pucch, p_srs_offset;      /* p_srs_offset: the RRC value pSRS-Offset 0..15 */
+} mi_ul_power_cfg_t;
+#define MI_UL_P_CMAX 23.0f              /* dBm, power class 3; every result is capped at it */
+/* P_PUSCH = 10 log10(L_prb) + P0 + alpha PL + Delta_TF.  P0 = p0_nominal_pusch + p0_ue_pusch; for a grant of the
+ * random-access response (p0_preamble != 0) P0 = p0_preamble + delta_preamble_msg3 and alpha = 1.  Delta_TF =
+ * 10 log10(2^(1.25 BPRE) - 1), BPRE = sum_Kr / (144 L_prb) (sum_Kr: the code-block sizes of the TB in bits; 12
+ * data symbols), when delta_mcs_based, else 0 */
+float mi_ul_pusch_power(const mi_ul_power_cfg_t *p, float PL, float p0_preamble, uint32_t L_prb, uint32_t sum_Kr);
+/* P_PUCCH = p0_nominal_pucch + p0_ue_pucch + PL + h(n_cqi, n_harq) + Delta_F(format).  format: MI_PUCCH_*; h =
+ * 10 log10(n_cqi / 4) for formats 2/2a/2b with n_cqi >= 4, else 0 (normal CP) */
+float mi_ul_pucch_power(const mi_ul_power_cfg_t *p, float PL, uint32_t format, uint32_t n_cqi, uint32_t n_harq);
+/* P_SRS = P_SRS_OFFSET + 10 log10(m_srs) + P0_PUSCH + alpha PL.  P_SRS_OFFSET = -3 + p_srs_offset when
+ * delta_mcs_based (K_S = 1.25), else -10.5 + 1.5 p_srs_offset */
+float mi_ul_srs_power(const mi_ul_power_cfg_t *p, float PL, uint32_t m_srs);
 
 #ifdef __cplusplus
 }

@@ -9,9 +9,9 @@
  * ue_dl.chest, ue_dl.pdcch, ue_dl.last_n_cce, ue_dl.last_location) are kept.
  *
  * Beyond the DL data path the header also carries the SURVEY.md 8f rows built on the GPU: DL control
- * (PDCCH/DCI, PHICH), the sync tracking subset and the UL PUSCH encoder.  Cell search / MIB, PUCCH and the PRACH
- * preamble exist under the library's own mi_* names; SRS, power control and the radio still come from srsLTE
- * itself.
+ * (PDCCH/DCI, PHICH), the sync tracking subset and the UL PUSCH encoder.  Cell search / MIB, PUCCH, the PRACH
+ * preamble, SRS and open-loop UL power control exist under the library's own mi_* names; the radio still comes
+ * from srsLTE itself.
  *
  * Conventions: 0 = SRSLTE_SUCCESS, -1 = SRSLTE_ERROR; srslte_pdsch_decode_rnti returns 0 iff
  * the TB CRC passes; payload bits are packed MSB first.
@@ -287,10 +287,11 @@ SRSLTE_API void srslte_vec_free(void *ptr);
  * CQI (uci_cqi / uci_cqi_len, up to 64 bits: the (32, O) block code up to 11 bits, CRC8 + tail-biting
  * convolutional code above) and RI (uci_ri / uci_ri_len, 1 or 2 bits).  Limits: PUSCH hopping type 1 only (36.213 8.4.1: DCI format 0 hopping
  * bits through srslte_dci_msg_to_ul_grant's n_rb_ho, intra- or inter-subframe mode from set_cfg's hopping
- * configuration; type 2 returns SRSLTE_ERROR), L_prb >= 3; SRS and UL
- * power control stay in srsLTE.  PUCCH formats 1/1a/1b and 2/2a/2b are available under the library's own name,
- * mi_ue_ul_pucch_encode below (and batched as mi_pucch_* in mi_ul.h).  set_cfg uses the DMRS, hopping, UCI and
- * PUCCH configurations (pucch_cfg, pucch_sched), the others are accepted.  set_normalization(true) scales by nof_prb / (15 sqrt(L_prb)) (srsLTE's factor as recorded
+ * configuration; type 2 returns SRSLTE_ERROR), L_prb >= 3; PUSCH is not
+ * shortened in cell-specific SRS subframes.  PUCCH formats 1/1a/1b and 2/2a/2b, the SRS and open-loop UL power
+ * control are available under the library's own names, mi_ue_ul_pucch_encode, mi_ue_ul_srs_encode and
+ * mi_ue_ul_*_power below (and as mi_pucch_*, mi_srs_*, mi_ul_*_power in mi_ul.h).  set_cfg keeps every
+ * configuration it is given.  set_normalization(true) scales by nof_prb / (15 sqrt(L_prb)) (srsLTE's factor as recorded
  * in DESIGN.md, unverified: srsLTE is not in the container); set_cfo(cfo) shifts the output by cfo
  * subcarrier spacings when set_cfo_enable(true). */
 #define SRSLTE_CQI_MAX_BITS 64
@@ -329,7 +330,7 @@ typedef struct SRSLTE_API {           /* phch_worker.cc:688-693 */
   uint32_t hopping_offset;
   uint32_t n_sb;
 } srslte_pusch_hopping_cfg_t;
-typedef struct SRSLTE_API {           /* accepted by set_cfg, used by srsLTE's SRS (out of scope) */
+typedef struct SRSLTE_API {           /* kept by set_cfg for mi_ue_ul_srs_encode (phch_worker.cc:721-730) */
   bool configured;
   uint32_t subframe_config, bw_cfg, I_srs, B, b_hop, n_rrc, k_tc, n_srs;
 } srslte_refsignal_srs_cfg_t;
@@ -344,7 +345,7 @@ typedef struct SRSLTE_API {
   uint32_t N_pucch_1, n_pucch_2, n_pucch_sr;
 } srslte_pucch_sched_t;
 typedef struct SRSLTE_API { uint32_t I_offset_cqi, I_offset_ri, I_offset_ack; } srslte_uci_cfg_t;
-typedef struct SRSLTE_API {           /* accepted by set_cfg (UL power control: out of scope) */
+typedef struct SRSLTE_API {           /* kept by set_cfg for mi_ue_ul_*_power (phch_worker.cc:732-746) */
   float p0_nominal_pusch, alpha, p0_nominal_pucch, delta_f_pucch[5], delta_preamble_msg3, p0_ue_pusch;
   bool delta_mcs_based, acc_enabled;
   float p0_ue_pucch, p_srs_offset;
@@ -422,6 +423,27 @@ SRSLTE_API int srslte_ue_ul_pusch_encode_rnti_softbuffer(srslte_ue_ul_t *q, uint
  * uci_data holds nothing to send. */
 SRSLTE_API int mi_ue_ul_pucch_encode(srslte_ue_ul_t *q, srslte_uci_data_t uci_data, uint32_t pdcch_n_cce,
                                      uint32_t tti, cf_t *output_signal);
+/* SRS (36.211 5.5.3, srsue_amd/csrc/srs.hip): the arguments and return convention of the SRS encode call of srsUE's
+ * worker (phch_worker.cc:641), under the library's own name.  The periodic SRS of set_cfg's srs_cfg for subframe tti
+ * (0..10239), with dmrs_cfg's group / sequence hopping flags and delta_ss: symbols 0..12 of the subframe are zero,
+ * symbol 13 carries the SRS.  Encodes on the instance's stream and copies the subframe (SRSLTE_SF_LEN_PRB samples) to
+ * output_signal; the PUSCH grant, the PUCCH plan and the softbuffers are untouched.  set_normalization(true) scales
+ * by nof_prb / (15 sqrt(m_srs / 2)) (the PUSCH factor with L_prb = m_srs / 2, the same count of occupied
+ * subcarriers; unverified against srsLTE like it); set_cfo applies as for PUSCH.  Whether tti is an SRS instant is
+ * not checked: srsUE decides that (phch_worker.cc:529-536).  Limits: FDD, normal CP, one antenna port, no aperiodic
+ * SRS; srsUE's worker never sends the SRS together with PUSCH or PUCCH in one subframe (mi_srs_batch_* in mi_ul.h
+ * can lay it over a shortened PUCCH).  Returns SRSLTE_ERROR (mi_last_error) when srs_cfg.configured is false or
+ * the configuration is rejected (mi_srs_resource). */
+SRSLTE_API int mi_ue_ul_srs_encode(srslte_ue_ul_t *q, uint32_t tti, cf_t *output_signal);
+/* Open-loop UL power control (36.213 5.1; mi_ul_pusch_power, mi_ul_pucch_power, mi_ul_srs_power of mi_ul.h on
+ * set_cfg's power_ctrl) with the argument lists of srsUE's worker (phch_worker.cc:568, :622, :652); dBm, capped at
+ * P_CMAX = 23.  _pusch_power: of the grant planned by the last srslte_ue_ul_cfg_grant, p0_preamble != 0 marks a
+ * grant of the random-access response; _pucch_power: format 0..5 = 1, 1a, 1b, 2, 2a, 2b (q->last_pucch_format);
+ * _srs_power: m_srs of set_cfg's srs_cfg (0 when SRS is not configured or rejected).  Limit: no TPC accumulation
+ * (f(i) = g(i) = 0; acc_enabled is stored and unused). */
+SRSLTE_API float mi_ue_ul_pusch_power(srslte_ue_ul_t *q, float PL, float p0_preamble);
+SRSLTE_API float mi_ue_ul_pucch_power(srslte_ue_ul_t *q, float PL, uint32_t format, uint32_t n_cqi, uint32_t n_harq);
+SRSLTE_API float mi_ue_ul_srs_power(srslte_ue_ul_t *q, float PL);
 SRSLTE_API int srslte_softbuffer_tx_init(srslte_softbuffer_tx_t *q, uint32_t nof_prb);
 SRSLTE_API void srslte_softbuffer_tx_reset(srslte_softbuffer_tx_t *q);
 SRSLTE_API void srslte_softbuffer_tx_free(srslte_softbuffer_tx_t *q);
@@ -513,11 +535,12 @@ SRSLTE_API int srslte_refsignal_srs_send_cs(uint32_t subframe_config, uint32_t s
 SRSLTE_API int srslte_refsignal_srs_send_ue(uint32_t I_srs, uint32_t tti);
 SRSLTE_API void srslte_ra_pusch_fprint(FILE *f, srslte_ra_ul_dci_t *q, uint32_t nof_prb);
 
-/* ---- OUT OF SCOPE (SURVEY.md 8 / DESIGN.md 9): SRS and UL power control are not implemented, and no srslte_*
- * PUCCH, PRACH or CFO name is exported.  They are declared so srsUE compiles against this header unchanged: an
- * integration links srsLTE's own modules rebuilt against this header, or stubs.  PUCCH and the
- * PRACH preamble exist under the library's own names: mi_ue_ul_pucch_encode above and mi_pucch_* in mi_ul.h,
- * mi_prach_init / _gen / _gen_cfo at the end of this header and mi_prach_* in mi_ul.h. -------- */
+/* ---- OUT OF SCOPE (SURVEY.md 8 / DESIGN.md 9): no srslte_* PUCCH, SRS, power-control, PRACH or CFO name is
+ * exported.  They are declared so srsUE compiles against this header unchanged: an integration links srsLTE's own
+ * modules rebuilt against this header, or stubs.  PUCCH, SRS, UL power control and the PRACH
+ * preamble exist under the library's own names: mi_ue_ul_pucch_encode, mi_ue_ul_srs_encode and mi_ue_ul_*_power
+ * above and mi_pucch_*, mi_srs_*, mi_ul_*_power in mi_ul.h, mi_prach_init / _gen / _gen_cfo at the end of this
+ * header and mi_prach_* in mi_ul.h. -------- */
 SRSLTE_API void srslte_ue_ul_pregen_signals(srslte_ue_ul_t *q);
 SRSLTE_API int srslte_ue_ul_pucch_encode(srslte_ue_ul_t *q, srslte_uci_data_t uci_data, uint32_t pdcch_n_cce,
                                          uint32_t tti, cf_t *output_signal);

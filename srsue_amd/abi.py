@@ -193,6 +193,17 @@ def lib():
             "mi_prach_batch_iq_samples": (sz, [vp]),
             "mi_prach_batch_run": (C.c_int, [vp, vp, vp, vp, vp]),
             "mi_prach_batch_resource": (C.c_int, [vp, u32, vp]),
+            "mi_srs_resource": (C.c_int, [vp, vp]),
+            "mi_srs_resource_n": (u32, [vp, u32, vp]),
+            "mi_srs_batch_create": (vp, [vp, u32, u32]),
+            "mi_srs_batch_destroy": (None, [vp]),
+            "mi_srs_batch_iq_offset": (sz, [vp, u32]),
+            "mi_srs_batch_iq_samples": (sz, [vp]),
+            "mi_srs_batch_run": (C.c_int, [vp, vp, vp, vp, vp]),
+            "mi_srs_batch_resource": (C.c_int, [vp, u32, vp]),
+            "mi_ul_pusch_power": (C.c_float, [vp, C.c_float, C.c_float, u32, u32]),
+            "mi_ul_pucch_power": (C.c_float, [vp, C.c_float, u32, u32, u32]),
+            "mi_ul_srs_power": (C.c_float, [vp, C.c_float, u32]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -1180,3 +1191,119 @@ class PrachBatch:
         if lib().mi_prach_batch_resource(self.h, i, C.byref(r)):
             raise RuntimeError("mi_prach_batch_resource: " + last_error())
         return r
+
+
+# ---- SRS, periodic (include/mi_ul.h) ----------------------------------------------------------------
+SRS_FLAG_LAST_SYMBOL_ONLY = 1
+SRS_CFG_FIELDS = ("cell_id", "nof_prb", "tti", "bw_cfg", "B", "b_hop", "n_rrc", "k_tc", "n_srs", "I_srs",
+                  "group_hopping", "sequence_hopping", "delta_ss")
+
+
+class SrsCfg(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in SRS_CFG_FIELDS]
+
+
+class SrsRes(C.Structure):
+    _fields_ = [("m_srs", C.c_uint32), ("M_sc", C.c_uint32), ("k0", C.c_uint32), ("n_b", C.c_uint32 * 4)] + \
+        [(n, C.c_uint32) for n in ("n_SRS", "T_srs", "u", "v", "nzc", "q", "n_cs")]
+
+
+# the same layouts as numpy records, for mi_srs_resource_n over arrays of configurations
+SRS_CFG_DTYPE = np.dtype([(n, np.uint32) for n in SRS_CFG_FIELDS])
+SRS_RES_DTYPE = np.dtype([("m_srs", np.uint32), ("M_sc", np.uint32), ("k0", np.uint32), ("n_b", np.uint32, 4)] +
+                         [(n, np.uint32) for n in ("n_SRS", "T_srs", "u", "v", "nzc", "q", "n_cs")])
+
+
+def srs_cfg(cell_id=1, nof_prb=6, tti=0, bw_cfg=7, B=0, b_hop=3, n_rrc=0, k_tc=0, n_srs=0, I_srs=0, group_hopping=0,
+            sequence_hopping=0, delta_ss=0):
+    return SrsCfg(cell_id, nof_prb, tti, bw_cfg, B, b_hop, n_rrc, k_tc, n_srs, I_srs, group_hopping, sequence_hopping,
+                  delta_ss)
+
+
+def srs_resource(cfg):
+    """mi_srs_resource: the planned SrsRes; raises on a rejected configuration"""
+    r = SrsRes()
+    if lib().mi_srs_resource(C.byref(cfg), C.byref(r)):
+        raise RuntimeError("mi_srs_resource: " + last_error())
+    return r
+
+
+def srs_resource_n(cfgs):
+    """mi_srs_resource_n over a SRS_CFG_DTYPE array: (records planned before the first rejection, their count)"""
+    cfgs = np.ascontiguousarray(cfgs, SRS_CFG_DTYPE)
+    out = np.zeros(len(cfgs), SRS_RES_DTYPE)
+    n = lib().mi_srs_resource_n(cfgs.ctypes.data, len(cfgs), out.ctypes.data)
+    return out[:n], n
+
+
+class SrsBatch:
+    """Owns one mi_srs_batch_t: N SRS transmissions planned once; run() encodes them into device IQ."""
+
+    def __init__(self, cfgs, flags=0):
+        self.cfgs = list(cfgs)
+        self._arr = (SrsCfg * len(self.cfgs))(*self.cfgs)
+        self.h = lib().mi_srs_batch_create(C.cast(self._arr, C.c_void_p), len(self.cfgs), flags)
+        if not self.h:
+            raise RuntimeError("mi_srs_batch_create: " + last_error())
+
+    def close(self):
+        if self.h:
+            lib().mi_srs_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def iq_samples(self):
+        return lib().mi_srs_batch_iq_samples(self.h)
+
+    def iq_offset(self, i):
+        return lib().mi_srs_batch_iq_offset(self.h, i)
+
+    def run(self, d_iq_ptr, stream_ptr=None, d_cfo_ptr=None, d_scale_ptr=None):
+        if lib().mi_srs_batch_run(self.h, C.c_void_p(d_cfo_ptr or 0), C.c_void_p(d_scale_ptr or 0),
+                                  C.c_void_p(d_iq_ptr), C.c_void_p(stream_ptr or 0)):
+            raise RuntimeError("mi_srs_batch_run: " + last_error())
+
+    def resource(self, i):
+        r = SrsRes()
+        if lib().mi_srs_batch_resource(self.h, i, C.byref(r)):
+            raise RuntimeError("mi_srs_batch_resource: " + last_error())
+        return r
+
+
+# ---- open-loop UL power control (include/mi_ul.h), host only ----------------------------------------
+P_CMAX = 23.0
+
+
+class UlPowerCfg(C.Structure):
+    _fields_ = [("p0_nominal_pusch", C.c_float), ("alpha", C.c_float), ("p0_nominal_pucch", C.c_float),
+                ("delta_f_pucch", C.c_float * 5), ("delta_preamble_msg3", C.c_float), ("p0_ue_pusch", C.c_float),
+                ("delta_mcs_based", C.c_uint32), ("acc_enabled", C.c_uint32), ("p0_ue_pucch", C.c_float),
+                ("p_srs_offset", C.c_float)]
+
+
+def ul_power_cfg(p0_nominal_pusch=-80.0, alpha=0.8, p0_nominal_pucch=-100.0, delta_f_pucch=(0.0, 1.0, 0.0, 0.0, 2.0),
+                 delta_preamble_msg3=4.0, p0_ue_pusch=0.0, delta_mcs_based=0, acc_enabled=0, p0_ue_pucch=0.0,
+                 p_srs_offset=7.0):
+    return UlPowerCfg(p0_nominal_pusch, alpha, p0_nominal_pucch, (C.c_float * 5)(*delta_f_pucch), delta_preamble_msg3,
+                      p0_ue_pusch, int(delta_mcs_based), int(acc_enabled), p0_ue_pucch, p_srs_offset)
+
+
+def ul_pusch_power(cfg, PL, p0_preamble=0.0, L_prb=1, sum_Kr=0):
+    """mi_ul_pusch_power (36.213 5.1.1.1), dBm"""
+    return lib().mi_ul_pusch_power(C.byref(cfg), PL, p0_preamble, L_prb, sum_Kr)
+
+
+def ul_pucch_power(cfg, PL, format=PUCCH_1A, n_cqi=0, n_harq=0):
+    """mi_ul_pucch_power (36.213 5.1.2.1), dBm"""
+    return lib().mi_ul_pucch_power(C.byref(cfg), PL, format, n_cqi, n_harq)
+
+
+def ul_srs_power(cfg, PL, m_srs=4):
+    """mi_ul_srs_power (36.213 5.1.3.1), dBm"""
+    return lib().mi_ul_srs_power(C.byref(cfg), PL, m_srs)

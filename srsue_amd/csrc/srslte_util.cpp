@@ -5,6 +5,23 @@
 #include <string.h>
 
 #include "srslte/srslte.h"
+#include "srs.h"
+
+namespace mi {
+// 36.213 Table 8.2-1 (FDD): UE-specific SRS periodicity T_SRS and subframe offset T_offset of I_SRS; -1: reserved.
+// The one copy of the table: srslte_refsignal_srs_send_ue below and the SRS planner (srs_host.cpp) read it here
+int srs_ue_period(uint32_t I, uint32_t* T, uint32_t* offset) {
+  static const uint32_t lim[] = {1, 6, 16, 36, 76, 156, 316, 636}, per[] = {2, 5, 10, 20, 40, 80, 160, 320};
+  static const uint32_t base[] = {0, 2, 7, 17, 37, 77, 157, 317};
+  for (int i = 0; i < 8; i++)
+    if (I <= lim[i]) {
+      *T = per[i];
+      *offset = I - base[i];
+      return 0;
+    }
+  return -1;
+}
+}  // namespace mi
 
 extern "C" {
 
@@ -63,11 +80,9 @@ int srslte_refsignal_srs_send_cs(uint32_t cfg, uint32_t sf_idx) {
 
 // 36.213 Table 8.2-1 (FDD): UE-specific SRS periodicity T_SRS and offset of I_SRS
 int srslte_refsignal_srs_send_ue(uint32_t I, uint32_t tti) {
-  static const uint32_t lim[] = {1, 6, 16, 36, 76, 156, 316, 636}, per[] = {2, 5, 10, 20, 40, 80, 160, 320};
-  static const uint32_t base[] = {0, 2, 7, 17, 37, 77, 157, 317};
-  for (int i = 0; i < 8; i++)
-    if (I <= lim[i]) return periodic(tti, per[i], I - base[i]) ? 1 : 0;
-  return -1;
+  uint32_t T, off;
+  if (mi::srs_ue_period(I, &T, &off)) return -1;
+  return periodic(tti, T, off) ? 1 : 0;
 }
 
 // wideband CQI from the reference-signal SNR (dB): the SNR thresholds of CQI 1..15 srsLTE 1.0 used for

@@ -5,7 +5,9 @@
 // UlEngine planned for the current grant (cfg_grant), a device payload buffer and a device subframe.
 // A retransmission (rv > 0) re-encodes the TB kept in the HARQ softbuffer: the circular buffer is a
 // deterministic function of the TB, so this equals srsLTE's reuse of its stored coded bits.
-// mi_ue_ul_pucch_encode (PUCCH, pucch.hip) shares the instance's stream and output staging and nothing else.
+// mi_ue_ul_pucch_encode (PUCCH, pucch.hip) and mi_ue_ul_srs_encode (SRS, srs.hip) share the instance's stream and
+// output staging and nothing else.  mi_ue_ul_pusch_power / _pucch_power / _srs_power are the open-loop power
+// control of ul_power.cpp on set_cfg's parameters.
 #include <time.h>
 #include <math.h>
 #include <stdlib.h>
@@ -14,6 +16,7 @@
 #include "../../include/srslte/srslte.h"
 #include "tables.h"
 #include "pucch_engine.h"
+#include "srs_engine.h"
 #include "ul_engine.h"
 #include "../../include/mi_ul.h"
 
@@ -33,6 +36,10 @@ struct mi_ue_ul_ctx {
   srslte_pucch_sched_t pucch_sched{};
   mi::DevBuf d_uci;
   uint32_t* h_uci = nullptr;
+  // SRS (mi_ue_ul_srs_encode): its own plan and table; set_cfg's SRS and power-control configurations
+  mi::SrsEngine srs;
+  srslte_refsignal_srs_cfg_t srs_cfg{};
+  mi_ul_power_cfg_t power{};
   // per-phase host-clock breakdown of pusch_encode (MI_UE_UL_PROF=1: the stream is synchronised at every
   // mark so GPU work is attributed to its phase; printed to stderr when the instance is freed):
   // 0 payload H2D, 1 plan, 2 table upload, 3 kernels, 4 IQ D2H + copy out
@@ -190,10 +197,25 @@ void srslte_ue_ul_set_cfo(srslte_ue_ul_t* q, float cur_cfo) {
   if (q) q->current_cfo = cur_cfo;
 }
 
-void srslte_ue_ul_set_cfg(srslte_ue_ul_t* q, srslte_refsignal_dmrs_pusch_cfg_t* dmrs_cfg, srslte_refsignal_srs_cfg_t*,
-                          srslte_pucch_cfg_t* pucch_cfg, srslte_pucch_sched_t* pucch_sched, srslte_uci_cfg_t* uci_cfg,
-                          srslte_pusch_hopping_cfg_t* hopping_cfg, srslte_ue_ul_powerctrl_t*) {
+void srslte_ue_ul_set_cfg(srslte_ue_ul_t* q, srslte_refsignal_dmrs_pusch_cfg_t* dmrs_cfg,
+                          srslte_refsignal_srs_cfg_t* srs_cfg, srslte_pucch_cfg_t* pucch_cfg,
+                          srslte_pucch_sched_t* pucch_sched, srslte_uci_cfg_t* uci_cfg,
+                          srslte_pusch_hopping_cfg_t* hopping_cfg, srslte_ue_ul_powerctrl_t* power_ctrl) {
   if (!q) return;
+  if (q->ctx && srs_cfg) q->ctx->srs_cfg = *srs_cfg;
+  if (q->ctx && power_ctrl) {
+    mi_ul_power_cfg_t& w = q->ctx->power;
+    w.p0_nominal_pusch = power_ctrl->p0_nominal_pusch;
+    w.alpha = power_ctrl->alpha;
+    w.p0_nominal_pucch = power_ctrl->p0_nominal_pucch;
+    for (int i = 0; i < 5; i++) w.delta_f_pucch[i] = power_ctrl->delta_f_pucch[i];
+    w.delta_preamble_msg3 = power_ctrl->delta_preamble_msg3;
+    w.p0_ue_pusch = power_ctrl->p0_ue_pusch;
+    w.delta_mcs_based = power_ctrl->delta_mcs_based ? 1 : 0;
+    w.acc_enabled = power_ctrl->acc_enabled ? 1 : 0;
+    w.p0_ue_pucch = power_ctrl->p0_ue_pucch;
+    w.p_srs_offset = power_ctrl->p_srs_offset;
+  }
   if (q->ctx && pucch_cfg) q->ctx->pucch_cfg = *pucch_cfg;
   if (q->ctx && pucch_sched) q->ctx->pucch_sched = *pucch_sched;
   if (dmrs_cfg) q->dmrs_cfg = *dmrs_cfg;
@@ -373,6 +395,67 @@ int mi_ue_ul_pucch_encode(srslte_ue_ul_t* q, srslte_uci_data_t uci, uint32_t pdc
   q->last_pucch_format = (uint32_t)format;
   q->pucch.shortened = p.shortened != 0;
   return SRSLTE_SUCCESS;
+}
+
+// SRS (36.211 5.5.3): srsUE's SRS encode call (phch_worker.cc:641) under the library's own name.  Planned from
+// set_cfg's SRS configuration and the DMRS configuration's hopping flags, encoded on the instance's stream by
+// srs.hip, the subframe copied to output_signal.  Whether tti is an SRS instant is the caller's decision
+// (phch_worker.cc:529-536).
+static void srs_cfg_of(const srslte_ue_ul_t* q, uint32_t tti, mi_srs_cfg_t* p) {
+  const srslte_refsignal_srs_cfg_t& s = q->ctx->srs_cfg;
+  *p = mi_srs_cfg_t{};
+  p->cell_id = q->cell.id;
+  p->nof_prb = q->cell.nof_prb;
+  p->tti = tti;
+  p->bw_cfg = s.bw_cfg;
+  p->B = s.B;
+  p->b_hop = s.b_hop;
+  p->n_rrc = s.n_rrc;
+  p->k_tc = s.k_tc;
+  p->n_srs = s.n_srs;
+  p->I_srs = s.I_srs;
+  p->group_hopping = q->dmrs_cfg.group_hopping_en;
+  p->sequence_hopping = q->dmrs_cfg.sequence_hopping_en;
+  p->delta_ss = q->dmrs_cfg.delta_ss;
+}
+
+int mi_ue_ul_srs_encode(srslte_ue_ul_t* q, uint32_t tti, cf_t* output_signal) {
+  if (!q || !q->ctx || !output_signal) return SRSLTE_ERROR_INVALID_INPUTS;
+  mi_ue_ul_ctx* c = q->ctx;
+  if (!c->srs_cfg.configured) { mi::set_error("SRS: not configured"); return SRSLTE_ERROR; }
+  mi_srs_cfg_t p;
+  srs_cfg_of(q, tti, &p);
+  if (c->srs.plan.build(&p, 1)) return SRSLTE_ERROR;   // every field checked: nothing is launched on an error
+  MiSrsTx& t = c->srs.plan.txs[0];
+  // the PUSCH factor with L_prb = m_srs / 2: the same count of occupied subcarriers
+  if (q->normalize_en) t.scale = (float)q->cell.nof_prb / 15.0f / sqrtf((float)c->srs.plan.res[0].m_srs / 2.0f);
+  if (q->cfo_en) t.cfo = q->current_cfo;
+  const size_t n = (size_t)15 * mi::symbol_sz(q->cell.nof_prb);
+  if (c->srs.upload(c->st) || c->srs.run(nullptr, nullptr, c->d_iq.p, c->st) ||
+      !mi::hip_ok(hipMemcpyAsync(c->h_iq, c->d_iq.p, n * 8, hipMemcpyDeviceToHost, c->st), "D2H IQ") ||
+      !mi::hip_ok(hipStreamSynchronize(c->st), "srs sync"))
+    return SRSLTE_ERROR;
+  memcpy(output_signal, c->h_iq, n * 8);
+  return SRSLTE_SUCCESS;
+}
+
+// Open-loop UL power control (36.213 5.1, ul_power.cpp) with srsUE's argument lists (phch_worker.cc:568, :622, :652)
+float mi_ue_ul_pusch_power(srslte_ue_ul_t* q, float PL, float p0_preamble) {
+  if (!q || !q->ctx) return 0.0f;
+  const srslte_cbsegm_t& s = q->pusch_cfg.cb_segm;   // of the grant planned by srslte_ue_ul_cfg_grant
+  return mi_ul_pusch_power(&q->ctx->power, PL, p0_preamble, q->pusch_cfg.grant.L_prb, s.C1 * s.K1 + s.C2 * s.K2);
+}
+float mi_ue_ul_pucch_power(srslte_ue_ul_t* q, float PL, uint32_t format, uint32_t n_cqi, uint32_t n_harq) {
+  if (!q || !q->ctx) return 0.0f;
+  return mi_ul_pucch_power(&q->ctx->power, PL, format, n_cqi, n_harq);
+}
+float mi_ue_ul_srs_power(srslte_ue_ul_t* q, float PL) {
+  if (!q || !q->ctx) return 0.0f;
+  mi_srs_cfg_t p;
+  mi_srs_res_t r;
+  srs_cfg_of(q, 0, &p);   // m_srs does not depend on the subframe
+  if (!q->ctx->srs_cfg.configured || mi_srs_resource(&p, &r)) return 0.0f;
+  return mi_ul_srs_power(&q->ctx->power, PL, r.m_srs);
 }
 
 int srslte_softbuffer_tx_init(srslte_softbuffer_tx_t* q, uint32_t nof_prb) {

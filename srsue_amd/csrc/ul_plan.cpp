@@ -39,10 +39,15 @@ int ul_dmrs_params(const mi_ul_cfg_t& c, uint32_t ns, uint32_t* q, uint32_t* nzc
   uint32_t prs = 0;
   for (int i = 0; i < 8; i++) prs += (uint32_t)s[8 * 7 * ns + i] << i;
   *ncs = (N1_DMRS[c.cyclic_shift & 7] + N2_DMRS[c.n_dmrs2 & 7] + prs) % 12;
+  ul_base_seq(M, u, v, q, nzc);
+  return 0;
+}
+
+void ul_base_seq(uint32_t M, uint32_t u, uint32_t v, uint32_t* q, uint32_t* nzc) {
   if (M < 36) {   // L_prb = 1, 2: the tabulated base sequences of group u (5.5.1.2), marked by N_ZC = 0
     *nzc = 0;
     *q = u;
-    return 0;
+    return;
   }
   uint32_t N = M - 1;
   while (!prime(N)) N--;
@@ -50,7 +55,6 @@ int ul_dmrs_params(const mi_ul_cfg_t& c, uint32_t ns, uint32_t* q, uint32_t* nzc
   const double qb = (double)N * (u + 1) / 31.0;
   const uint32_t odd = (uint32_t)floor(2.0 * qb) & 1u;
   *q = (uint32_t)floor(qb + 0.5) + (odd ? (uint32_t)-(int32_t)v : v);
-  return 0;
 }
 
 uint32_t ul_radix_plan(uint32_t n) {

@@ -14,6 +14,9 @@ namespace mi {
 
 // 36.211 5.5.2.1 / 5.5.1: DMRS root q, Zadoff-Chu length and cyclic shift of slot ns (0..19)
 int ul_dmrs_params(const mi_ul_cfg_t& c, uint32_t ns, uint32_t* q, uint32_t* nzc, uint32_t* ncs);
+// 36.211 5.5.1.1 / 5.5.1.2: root q and Zadoff-Chu length of the base sequence r_{u,v} of length M (a multiple of
+// 12); M < 36: the tabulated sequences, nzc = 0 and q = u.  Shared by the PUSCH DMRS and the SRS (srs_host.cpp)
+void ul_base_seq(uint32_t M, uint32_t u, uint32_t v, uint32_t* q, uint32_t* nzc);
 // radix list (8, 4, 2, 3, 5; 4 bits per stage) of an n-point transform, 0 if n has another factor
 uint32_t ul_radix_plan(uint32_t n);
 // CQI channel coding on PUSCH (36.212 5.2.2.6.4): the Q coded bits of the O-bit report o (O <= 11: the
