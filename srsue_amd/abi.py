@@ -1060,19 +1060,23 @@ def pucch_select(ack_len=0, sr=False, cqi_len=0, simul_cqi_ack_dropped=False, n_
     return None if f < 0 else (f, n.value)
 
 
-class PucchBatch:
-    """Owns one mi_pucch_batch_t: N PUCCH transmissions planned once; run() encodes them from device UCI words."""
+class _TxBatch:
+    """Owns one mi_<PREFIX>_batch_t of N transmissions planned once from CFG records; resource() returns a RES."""
+    PREFIX = CFG = RES = None
 
-    def __init__(self, cfgs):
+    def __init__(self, cfgs, flags=0):
         self.cfgs = list(cfgs)
-        self._arr = (PucchCfg * len(self.cfgs))(*self.cfgs)
-        self.h = lib().mi_pucch_batch_create(C.cast(self._arr, C.c_void_p), len(self.cfgs), 0)
+        self._arr = (self.CFG * len(self.cfgs))(*self.cfgs)
+        self.h = self._fn("create")(C.cast(self._arr, C.c_void_p), len(self.cfgs), flags)
         if not self.h:
-            raise RuntimeError("mi_pucch_batch_create: " + last_error())
+            raise RuntimeError(f"mi_{self.PREFIX}_batch_create: " + last_error())
+
+    def _fn(self, name):
+        return getattr(lib(), f"mi_{self.PREFIX}_batch_{name}")
 
     def close(self):
         if self.h:
-            lib().mi_pucch_batch_destroy(self.h)
+            self._fn("destroy")(self.h)
             self.h = None
 
     def __del__(self):
@@ -1083,20 +1087,33 @@ class PucchBatch:
 
     @property
     def iq_samples(self):
-        return lib().mi_pucch_batch_iq_samples(self.h)
+        return self._fn("iq_samples")(self.h)
 
     def iq_offset(self, i):
-        return lib().mi_pucch_batch_iq_offset(self.h, i)
+        return self._fn("iq_offset")(self.h, i)
+
+    def resource(self, i):
+        r = self.RES()
+        if self._fn("resource")(self.h, i, C.byref(r)):
+            raise RuntimeError(f"mi_{self.PREFIX}_batch_resource: " + last_error())
+        return r
+
+    def _run_cfo_scale(self, d_iq_ptr, stream_ptr, d_cfo_ptr, d_scale_ptr):
+        if self._fn("run")(self.h, C.c_void_p(d_cfo_ptr or 0), C.c_void_p(d_scale_ptr or 0), C.c_void_p(d_iq_ptr),
+                           C.c_void_p(stream_ptr or 0)):
+            raise RuntimeError(f"mi_{self.PREFIX}_batch_run: " + last_error())
+
+
+class PucchBatch(_TxBatch):
+    """Owns one mi_pucch_batch_t: N PUCCH transmissions planned once; run() encodes them from device UCI words."""
+    PREFIX, CFG, RES = "pucch", PucchCfg, PucchRes
+
+    def __init__(self, cfgs):
+        super().__init__(cfgs, 0)
 
     def run(self, d_uci_ptr, d_iq_ptr, stream_ptr=None):
         if lib().mi_pucch_batch_run(self.h, C.c_void_p(d_uci_ptr), C.c_void_p(d_iq_ptr), C.c_void_p(stream_ptr or 0)):
             raise RuntimeError("mi_pucch_batch_run: " + last_error())
-
-    def resource(self, i):
-        r = PucchRes()
-        if lib().mi_pucch_batch_resource(self.h, i, C.byref(r)):
-            raise RuntimeError("mi_pucch_batch_resource: " + last_error())
-        return r
 
 
 # ---- PRACH preamble, formats 0-3 (include/mi_ul.h) --------------------------------------------------
@@ -1153,44 +1170,12 @@ def prach_send_tti(config_idx, tti, allowed_subframe=-1):
     return lib().mi_prach_send_tti(config_idx, tti, allowed_subframe)
 
 
-class PrachBatch:
+class PrachBatch(_TxBatch):
     """Owns one mi_prach_batch_t: N preambles planned once; run() generates them into device IQ."""
-
-    def __init__(self, cfgs, flags=0):
-        self.cfgs = list(cfgs)
-        self._arr = (PrachCfg * len(self.cfgs))(*self.cfgs)
-        self.h = lib().mi_prach_batch_create(C.cast(self._arr, C.c_void_p), len(self.cfgs), flags)
-        if not self.h:
-            raise RuntimeError("mi_prach_batch_create: " + last_error())
-
-    def close(self):
-        if self.h:
-            lib().mi_prach_batch_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def iq_samples(self):
-        return lib().mi_prach_batch_iq_samples(self.h)
-
-    def iq_offset(self, i):
-        return lib().mi_prach_batch_iq_offset(self.h, i)
+    PREFIX, CFG, RES = "prach", PrachCfg, PrachRes
 
     def run(self, d_iq_ptr, stream_ptr=None, d_cfo_ptr=None, d_scale_ptr=None):
-        if lib().mi_prach_batch_run(self.h, C.c_void_p(d_cfo_ptr or 0), C.c_void_p(d_scale_ptr or 0),
-                                    C.c_void_p(d_iq_ptr), C.c_void_p(stream_ptr or 0)):
-            raise RuntimeError("mi_prach_batch_run: " + last_error())
-
-    def resource(self, i):
-        r = PrachRes()
-        if lib().mi_prach_batch_resource(self.h, i, C.byref(r)):
-            raise RuntimeError("mi_prach_batch_resource: " + last_error())
-        return r
+        self._run_cfo_scale(d_iq_ptr, stream_ptr, d_cfo_ptr, d_scale_ptr)
 
 
 # ---- SRS, periodic (include/mi_ul.h) ----------------------------------------------------------------
@@ -1236,44 +1221,12 @@ def srs_resource_n(cfgs):
     return out[:n], n
 
 
-class SrsBatch:
+class SrsBatch(_TxBatch):
     """Owns one mi_srs_batch_t: N SRS transmissions planned once; run() encodes them into device IQ."""
-
-    def __init__(self, cfgs, flags=0):
-        self.cfgs = list(cfgs)
-        self._arr = (SrsCfg * len(self.cfgs))(*self.cfgs)
-        self.h = lib().mi_srs_batch_create(C.cast(self._arr, C.c_void_p), len(self.cfgs), flags)
-        if not self.h:
-            raise RuntimeError("mi_srs_batch_create: " + last_error())
-
-    def close(self):
-        if self.h:
-            lib().mi_srs_batch_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def iq_samples(self):
-        return lib().mi_srs_batch_iq_samples(self.h)
-
-    def iq_offset(self, i):
-        return lib().mi_srs_batch_iq_offset(self.h, i)
+    PREFIX, CFG, RES = "srs", SrsCfg, SrsRes
 
     def run(self, d_iq_ptr, stream_ptr=None, d_cfo_ptr=None, d_scale_ptr=None):
-        if lib().mi_srs_batch_run(self.h, C.c_void_p(d_cfo_ptr or 0), C.c_void_p(d_scale_ptr or 0),
-                                  C.c_void_p(d_iq_ptr), C.c_void_p(stream_ptr or 0)):
-            raise RuntimeError("mi_srs_batch_run: " + last_error())
-
-    def resource(self, i):
-        r = SrsRes()
-        if lib().mi_srs_batch_resource(self.h, i, C.byref(r)):
-            raise RuntimeError("mi_srs_batch_resource: " + last_error())
-        return r
+        self._run_cfo_scale(d_iq_ptr, stream_ptr, d_cfo_ptr, d_scale_ptr)
 
 
 # ---- open-loop UL power control (include/mi_ul.h), host only ----------------------------------------

@@ -51,6 +51,10 @@ __host__ __device__ inline int symbol_sz(uint32_t nof_prb) {
   return nof_prb <= 6 ? 128 : nof_prb <= 15 ? 256 : nof_prb <= 25 ? 512 : nof_prb <= 50 ? 1024
        : nof_prb <= 75 ? 1536 : nof_prb <= 110 ? 2048 : -1;
 }
+// the six LTE channel bandwidths (36.101 Table 5.6-1); symbol_sz also takes what lies between them
+__host__ __device__ inline bool std_nof_prb(uint32_t nof_prb) {
+  return nof_prb == 6 || nof_prb == 15 || nof_prb == 25 || nof_prb == 50 || nof_prb == 75 || nof_prb == 100;
+}
 __host__ __device__ inline int cp_len(int N, int l_in_slot) { return (l_in_slot == 0 ? 160 : 144) * N / 2048; }
 __host__ __device__ inline int sf_len(int N) { return 15 * N; }
 // sample offset of the useful part of OFDM symbol l (0..13) inside the subframe

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "prach.h"
+#include "ul_seq_dev.h"
 
 namespace mi {
 namespace {
@@ -28,12 +29,6 @@ constexpr uint32_t ROOT_PARTS = 4;       // lanes that share one bin of the root
 constexpr uint32_t ROOT_K = T / ROOT_PARTS;                    // 64 bins per workgroup
 constexpr uint32_t ROOT_SPLIT = (NZC + ROOT_K - 1) / ROOT_K;   // 14 workgroups per root
 
-__device__ __forceinline__ float2 cmulf(float2 a, float2 b) {
-  return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 mulj(float2 a) { return make_float2(-a.y, a.x); }
 // exp(j 2 pi num / den), 0 <= num < den < 2^24
 __device__ __forceinline__ float2 unit(uint32_t num, uint32_t den) {
   float s, c;
@@ -41,23 +36,8 @@ __device__ __forceinline__ float2 unit(uint32_t num, uint32_t den) {
   return make_float2(c, s);
 }
 
-// unnormalised inverse DFTs of 3 and 8 points in registers (exp(+j ...))
-__device__ __forceinline__ void idft(float2 (&v)[3]) {
-  const float2 t = cadd(v[1], v[2]), d = csub(v[1], v[2]);
-  const float2 m = make_float2(v[0].x - 0.5f * t.x, v[0].y - 0.5f * t.y);
-  const float h = 0.86602540378443865f;
-  const float2 s = make_float2(-h * d.y, h * d.x);
-  v[0] = cadd(v[0], t);
-  v[1] = cadd(m, s);
-  v[2] = csub(m, s);
-}
-__device__ __forceinline__ void idft4(float2& a0, float2& a1, float2& a2, float2& a3) {
-  const float2 s0 = cadd(a0, a2), s1 = csub(a0, a2), s2 = cadd(a1, a3), s3 = mulj(csub(a1, a3));
-  a0 = cadd(s0, s2);
-  a1 = cadd(s1, s3);
-  a2 = csub(s0, s2);
-  a3 = csub(s1, s3);
-}
+// unnormalised inverse DFT of 8 points in registers (exp(+j ...)), on the shared 4-point one and beside the 3-point one
+using mi::idft;
 __device__ __forceinline__ void idft(float2 (&v)[8]) {
   idft4(v[0], v[2], v[4], v[6]);   // E(k) in v[0], v[2], v[4], v[6]
   idft4(v[1], v[3], v[5], v[7]);   // O(k) in v[1], v[3], v[5], v[7]
@@ -89,7 +69,7 @@ __device__ __forceinline__ void pass(const float2* __restrict__ in, float2* __re
     if (NS > 1) {
       const uint32_t step = k * (NF / (NS * R));
 #pragma unroll
-      for (uint32_t r = 1; r < R; r++) v[r] = cmulf(v[r], tw[r * step]);
+      for (uint32_t r = 1; r < R; r++) v[r] = cmul(v[r], tw[r * step]);
     }
     idft(v);
     const uint32_t j0 = (j / NS) * (NS * R) + k;
@@ -121,7 +101,7 @@ __global__ __launch_bounds__(PRACH_THREADS) void prach_root_kernel(const uint32_
   float2 acc = make_float2(0.0f, 0.0f);
   uint32_t idx = (part * k) % NZC;
   for (uint32_t n = part; n < NZC; n += ROOT_PARTS) {
-    const float2 p = cmulf(xu[n], tw[idx]);
+    const float2 p = cmul(xu[n], tw[idx]);
     acc.x += p.x;
     acc.y += p.y;
     idx += step;
@@ -162,7 +142,7 @@ __global__ __launch_bounds__(PRACH_THREADS) void prach_gen_kernel(const MiPrachT
       if (k < NZC) {
         uint32_t b = x.first_bin + k;
         b = b >= x.N_ifft ? b - x.N_ifft : b;
-        z = cmulf(cmulf(Xu[k], unit((x.C_v * k) % NZC, NZC)), unit((b * r) % x.N_ifft, x.N_ifft));
+        z = cmul(cmul(Xu[k], unit((x.C_v * k) % NZC, NZC)), unit((b * r) % x.N_ifft, x.N_ifft));
       }
       Rq[p] = z;
     }
@@ -198,7 +178,7 @@ __global__ __launch_bounds__(PRACH_THREADS) void prach_gen_kernel(const MiPrachT
         ph -= floor(ph);
         float sv, cv;
         sincospif(2.0f * (float)ph, &sv, &cv);
-        y = cmulf(v, make_float2(cv, sv));
+        y = cmul(v, make_float2(cv, sv));
       }
       dst[pos[c]] = y;
     }

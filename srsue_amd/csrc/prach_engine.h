@@ -1,4 +1,4 @@
-// prach_engine.h -- device tables + launch of one PRACH plan (shared by the batched ABI, prach_batch.cpp, and the
+// prach_engine.h -- device tables + launch of one PRACH plan (shared by the batched ABI, ul_ctrl_batch.cpp, and the
 // per-call mi_prach_gen / mi_prach_gen_cfo, ue_prach.cpp).
 #pragma once
 #include "engine.h"

@@ -111,10 +111,6 @@ int format_of(uint32_t config_idx) {
   return (int)(config_idx / 16);
 }
 
-bool valid_prb(uint32_t nof_prb) {
-  return nof_prb == 6 || nof_prb == 15 || nof_prb == 25 || nof_prb == 50 || nof_prb == 75 || nof_prb == 100;
-}
-
 // srsUE configures one cell at a time: its 64 preambles are derived once per thread and configuration
 struct CellMemo {
   uint32_t root = 0xFFFFFFFFu, zczc = 0, hs = 0;
@@ -124,7 +120,7 @@ thread_local CellMemo g_cell;
 
 // every field of c; the cell's preambles to *cell.  false + set_error
 bool check(const mi_prach_cfg_t& c, const PrachCell** cell) {
-  if (!valid_prb(c.nof_prb)) {
+  if (!std_nof_prb(c.nof_prb)) {
     set_error("PRACH: nof_prb must be one of 6, 15, 25, 50, 75, 100");
     return false;
   }

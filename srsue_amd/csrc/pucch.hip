@@ -11,49 +11,11 @@
 #include <hip/hip_runtime.h>
 
 #include "pucch.h"
+#include "ul_seq_dev.h"
 
 namespace mi {
 
-// 36.211 Table 5.5.1.2-1: phi(n) of the base sequences r_u(n) = exp(j phi(n) pi / 4), M_sc = 12, group u = 0..29.
-// The same rows as UL_PHI12 of ul.hip (device constants are per translation unit); tests/test_gpu_pucch.py runs
-// every group against the oracle's copy.
-__constant__ int8_t PUCCH_PHI12[30][12] = {
-    {-1,  1,  3, -3,  3,  3,  1,  1,  3,  1, -3,  3},
-    { 1,  1,  3,  3,  3, -1,  1, -3, -3,  1, -3,  3},
-    { 1,  1, -3, -3, -3, -1, -3, -3,  1, -3,  1, -1},
-    {-1,  1,  1,  1,  1, -1, -3, -3,  1, -3,  3, -1},
-    {-1,  3,  1, -1,  1, -1, -3, -1,  1, -1,  1,  3},
-    { 1, -3,  3, -1, -1,  1,  1, -1, -1,  3, -3,  1},
-    {-1,  3, -3, -3, -3,  3,  1, -1,  3,  3, -3,  1},
-    {-3, -1, -1, -1,  1, -3,  3, -1,  1, -3,  3,  1},
-    { 1, -3,  3,  1, -1, -1, -1,  1,  1,  3, -1,  1},
-    { 1, -3, -1,  3,  3, -1, -3,  1,  1,  1,  1,  1},
-    {-1,  3, -1,  1,  1, -3, -3, -1, -3, -3,  3, -1},
-    { 3,  1, -1, -1,  3,  3, -3,  1,  3,  1,  3,  3},
-    { 1, -3,  1,  1, -3,  1,  1,  1, -3, -3, -3,  1},
-    { 3,  3, -3,  3, -3,  1,  1,  3, -1, -3,  3,  3},
-    {-3,  1, -1, -3, -1,  3,  1,  3,  3,  3, -1,  1},
-    { 3, -1,  1, -3, -1, -1,  1,  1,  3,  1, -1, -3},
-    { 1,  3,  1, -1,  1,  3,  3,  3, -1, -1,  3, -1},
-    {-3,  1,  1,  3, -3,  3, -3, -3,  3,  1,  3, -1},
-    {-3,  3,  1,  1, -3,  1, -3, -3, -1, -1,  1, -3},
-    {-1,  3,  1,  3,  1, -1, -1,  3, -3, -1, -3, -1},
-    {-1, -3,  1,  1,  1,  1,  3,  1, -1,  1, -3, -1},
-    {-1,  3, -1,  1, -3, -3, -3, -3, -3,  1, -1, -3},
-    { 1,  1, -3, -3, -3, -3, -1,  3, -3,  1, -3,  3},
-    { 1,  1, -1, -3, -1, -3,  1, -1,  1,  3, -1,  1},
-    { 1,  1,  3,  1,  3,  3, -1,  1, -1, -3, -3,  1},
-    { 1, -3,  3,  3,  1,  3,  3,  1, -3, -1, -1,  3},
-    { 1,  3, -3, -3,  3, -3,  1, -1, -1,  3, -1, -3},
-    {-3, -1, -3, -1, -3,  3,  1, -1,  1,  3, -3, -3},
-    {-1,  3, -3,  3, -1,  3,  3, -3,  3,  3, -1, -1},
-    { 3, -3, -3, -1, -1, -3, -1,  3, -3,  3,  1, -1}};
-
 namespace {
-
-__device__ __forceinline__ float2 cmulf(float2 a, float2 b) {
-  return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
 
 // phase index (units of pi / 12) of the 1a / 1b constellation: 1 bit 0 -> 1, 1 -> -1; 2 bits (b0 b1) 00 -> 1,
 // 01 -> -j, 10 -> j, 11 -> -1 (36.211 Table 5.4.1-1)
@@ -119,7 +81,7 @@ __global__ __launch_bounds__(PUCCH_THREADS) void pucch_kernel(const MiPucchTx* _
   float2 c[12];
 #pragma unroll
   for (int k = 0; k < 12; k++) {
-    const uint32_t idx = (uint32_t)(3 * (int)PUCCH_PHI12[u][k] + 24) + 2u * ncs * (uint32_t)k + a;
+    const uint32_t idx = (uint32_t)(3 * (int)UL_PHI12[u][k] + 24) + 2u * ncs * (uint32_t)k + a;
     float sv, cv;
     sincospif((float)(idx % 24u) * (1.0f / 12.0f), &sv, &cv);
     c[k] = make_float2(cv, sv);
@@ -137,17 +99,11 @@ __global__ __launch_bounds__(PUCCH_THREADS) void pucch_kernel(const MiPucchTx* _
     float2 acc = c[11];
 #pragma unroll
     for (int k = 10; k >= 0; k--) {
-      acc = cmulf(acc, w);
+      acc = cmul(acc, w);
       acc.x += c[k].x;
       acc.y += c[k].y;
     }
-    // exp(j pi (2 k0 + 1) n / N), its argument reduced exactly in integers (|(2 k0 + 1) n| < 2^23), times the
-    // frequency offset srslte_ue_ul_set_cfo asks for (cfo subcarriers over the subframe's sample index)
-    int r = ((2 * k0 + 1) * n) % twoN;
-    r = r < 0 ? r + twoN : r;
-    sincospif(((float)r + 2.0f * x.cfo * (float)(pos + i)) * rN, &sv, &cv);
-    const float2 y = cmulf(acc, make_float2(cv, sv));
-    dst[i] = make_float2(y.x * gN, y.y * gN);
+    dst[i] = sc_shift_out(acc, 2 * k0 + 1, n, twoN, x.cfo, pos + i, rN, gN);
   }
 }
 

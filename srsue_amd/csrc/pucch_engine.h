@@ -1,4 +1,4 @@
-// pucch_engine.h -- device tables + launch of one PUCCH plan (shared by the batched ABI, pucch_batch.cpp, and
+// pucch_engine.h -- device tables + launch of one PUCCH plan (shared by the batched ABI, ul_ctrl_batch.cpp, and
 // the per-TTI mi_ue_ul_pucch_encode, ue_ul.cpp).
 #pragma once
 #include "engine.h"

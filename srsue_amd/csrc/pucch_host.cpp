@@ -7,33 +7,27 @@
 
 #include "plan.h"     // set_error
 #include "tables.h"   // gold_bits
-#include "ul_plan.h"  // ul_cqi_code
+#include "ul_plan.h"  // ul_cqi_code, ul_group_u
 
 namespace mi {
 namespace {
 
 constexpr uint32_t C_NORM = 3, D_NORM = 2, NSC = 12;   // c and d of 5.4.1 for the normal CP, N_sc^RB
 
-// what depends on the cell alone: n_cs^cell(ns, l) and f_gh(ns) of every slot of the frame
+// what depends on the cell alone: n_cs^cell(ns, l) of every slot of the frame
 struct CellSeq {
   uint32_t cell_id = 0xFFFFFFFFu;
   uint8_t ncs[20][7];
-  uint8_t fgh[20];
   void load(uint32_t id) {
     if (id == cell_id) return;
-    std::vector<uint8_t> c(8 * 7 * 20), g(8 * 20);
+    std::vector<uint8_t> c(8 * 7 * 20);
     gold_bits(id, (uint32_t)c.size(), c.data());        // 5.4: c_init = N_ID^cell
-    gold_bits(id / 30, (uint32_t)g.size(), g.data());   // 5.5.1.3: c_init = floor(N_ID^cell / 30)
-    for (uint32_t ns = 0; ns < 20; ns++) {
+    for (uint32_t ns = 0; ns < 20; ns++)
       for (uint32_t l = 0; l < 7; l++) {
         uint32_t v = 0;
         for (uint32_t i = 0; i < 8; i++) v += (uint32_t)c[8 * 7 * ns + 8 * l + i] << i;
         ncs[ns][l] = (uint8_t)(v % NSC);   // only n_cs^cell mod 12 enters n_cs
       }
-      uint32_t f = 0;
-      for (uint32_t i = 0; i < 8; i++) f += (uint32_t)g[8 * ns + i] << i;
-      fgh[ns] = (uint8_t)(f % 30);
-    }
     cell_id = id;
   }
 };
@@ -42,8 +36,7 @@ bool is_f2(uint32_t format) { return format >= MI_PUCCH_2; }
 
 // every field of c, and the resource block index m (5.4.3) it leads to; false + set_error
 bool check(const mi_pucch_cfg_t& c, uint32_t* m_out) {
-  if (symbol_sz(c.nof_prb) < 0 || (c.nof_prb != 6 && c.nof_prb != 15 && c.nof_prb != 25 && c.nof_prb != 50 &&
-                                   c.nof_prb != 75 && c.nof_prb != 100)) {
+  if (!std_nof_prb(c.nof_prb)) {
     set_error("PUCCH: nof_prb must be one of 6, 15, 25, 50, 75, 100");
     return false;
   }
@@ -105,7 +98,7 @@ void derive(const mi_pucch_cfg_t& c, uint32_t m, CellSeq& cs, mi_pucch_res_t* r)
   for (uint32_t s = 0; s < 2; s++) {
     const uint32_t ns = 2 * c.sf_idx + s;
     r->n_prb[s] = (m + s) % 2 == 0 ? m / 2 : c.nof_prb - 1 - m / 2;
-    r->u[s] = ((c.group_hopping ? cs.fgh[ns] : 0u) + c.cell_id % 30) % 30;
+    r->u[s] = ul_group_u(c.cell_id, ns, c.group_hopping, c.cell_id % 30);
     r->n_prime[s] = np[s];
     r->n_oc[s] = is_f2(c.format) ? 0 : np[s] * D / Np;
     const uint32_t off = is_f2(c.format) ? np[s] : (np[s] * D + r->n_oc[s] % D) % Np;

@@ -14,74 +14,18 @@
 #include <hip/hip_runtime.h>
 
 #include "srs.h"
+#include "ul_seq_dev.h"
 
 namespace mi {
 
-// 36.211 Table 5.5.1.2-2: phi(n) of the base sequences r_u(n) = exp(j phi(n) pi / 4), M_sc = 24, group u = 0..29.
-// The same rows as UL_PHI24 of ul.hip (device constants are per translation unit); tests/test_gpu_srs.py runs
-// every group against the oracle's copy.
-__constant__ int8_t SRS_PHI24[30][24] = {
-    {-1,  3,  1, -3,  3, -1,  1,  3, -3,  3,  1,  3, -3,  3,  1,  1, -1,  1,  3, -3,  3, -3, -1, -3},
-    {-3,  3, -3, -3, -3,  1, -3, -3,  3, -1,  1,  1,  1,  3,  1, -1,  3, -3, -3,  1,  3,  1,  1, -3},
-    { 3, -1,  3,  3,  1,  1, -3,  3,  3,  3,  3,  1, -1,  3, -1,  1,  1, -1, -3, -1, -1,  1,  3,  3},
-    {-1, -3,  1,  1,  3, -3,  1,  1, -3, -1, -1,  1,  3,  1,  3,  1, -1,  3,  1,  1, -3, -1, -3, -1},
-    {-1, -1, -1, -3, -3, -1,  1,  1,  3,  3, -1,  3, -1,  1, -1, -3,  1, -1, -3, -3,  1, -3, -1, -1},
-    {-3,  1,  1,  3, -1,  1,  3,  1, -3,  1, -3,  1,  1, -1, -1,  3, -1, -3,  3, -3, -3, -3,  1,  1},
-    { 1,  1, -1, -1,  3, -3, -3,  3, -3,  1, -1, -1,  1, -1,  1,  1, -1, -3, -1,  1, -1,  3, -1, -3},
-    {-3,  3,  3, -1, -1, -3, -1,  3,  1,  3,  1,  3,  1,  1, -1,  3,  1, -1,  1,  3, -3, -1, -1,  1},
-    {-3,  1,  3, -3,  1, -1, -3,  3, -3,  3, -1, -1, -1, -1,  1, -3, -3, -3,  1, -3, -3, -3,  1, -3},
-    { 1,  1, -3,  3,  3, -1, -3, -1,  3, -3,  3,  3,  3, -1,  1,  1, -3,  1, -1,  1,  1, -3,  1,  1},
-    {-1,  1, -3, -3,  3, -1,  3, -1, -1, -3, -3, -3, -1, -3, -3,  1, -1,  1,  3,  3, -1,  1, -1,  3},
-    { 1,  3,  3, -3, -3,  1,  3,  1, -1, -3, -3, -3,  3,  3, -3,  3,  3, -1, -3,  3, -1,  1, -3,  1},
-    { 1,  3,  3,  1,  1,  1, -1, -1,  1, -3,  3, -1,  1,  1, -3,  3,  3, -1, -3,  3, -3, -1, -3, -1},
-    { 3, -1, -1, -1, -1, -3, -1,  3,  3,  1, -1,  1,  3,  3,  3, -1,  1,  1, -3,  1,  3, -1, -3,  3},
-    {-3, -3,  3,  1,  3,  1, -3,  3,  1,  3,  1,  1,  3,  3, -1, -1, -3,  1, -3, -1,  3,  1,  1,  3},
-    {-1, -1,  1, -3,  1,  3, -3,  1, -1, -3, -1,  3,  1,  3,  1, -1, -3, -3, -1, -1, -3, -3, -3, -1},
-    {-1, -3,  3, -1, -1, -1, -1,  1,  1, -3,  3,  1,  3,  3,  1, -1,  1, -3,  1, -3,  1,  1, -3, -1},
-    { 1,  3, -1,  3,  3, -1, -3,  1, -1, -3,  3,  3,  3, -1,  1,  1,  3, -1, -3, -1,  3, -1, -1, -1},
-    { 1,  1,  1,  1,  1, -1,  3, -1, -3,  1,  1,  3, -3,  1, -3, -1,  1,  1, -3, -3,  3,  1,  1, -3},
-    { 1,  3,  3,  1, -1, -3,  3, -1,  3,  3,  3, -3,  1, -1,  1, -1, -3, -1,  1,  3, -1,  3, -3, -3},
-    {-1, -3,  3, -3, -3, -3, -1, -1, -3, -1, -3,  3,  1,  3, -3, -1,  3, -1,  1, -1,  3, -3,  1, -1},
-    {-3, -3,  1,  1, -1,  1, -1,  1, -1,  3,  1, -3, -1,  1, -1,  1, -1, -1,  3,  3, -3, -1,  1, -3},
-    {-3, -1, -3,  3,  1, -1, -3, -1, -3, -3,  3, -3,  3, -3, -1,  1,  3,  1, -3,  1,  3,  3, -1, -3},
-    {-1, -1, -1, -1,  3,  3,  3,  1,  3,  3, -3,  1,  3, -1,  3, -1,  3,  3, -3,  3,  1, -1,  3,  3},
-    { 1, -1,  3,  3, -1, -3,  3, -3, -1, -1,  3, -1,  3, -1, -1,  1,  1,  1,  1, -1, -1, -3, -1,  3},
-    { 1, -1,  1, -1,  3, -1,  3,  1,  1, -1, -1, -3,  1,  1, -3,  1,  3, -3,  1,  1, -3, -3, -1, -1},
-    {-3, -1,  1,  3,  1,  1, -3, -1, -1, -3,  3, -3,  3,  1, -3,  3, -3,  1, -1,  1, -3,  1,  1,  1},
-    {-1, -3,  3,  3,  1,  1,  3, -1, -3, -1, -1, -1,  3,  1, -3, -3, -1,  3, -3, -1, -3, -1, -3, -1},
-    {-1, -3, -1, -1,  1, -3, -1, -1,  1, -1, -3,  1,  1, -3,  1, -3, -3,  3,  1,  1, -1,  3, -1, -1},
-    { 1,  1, -1, -1, -3, -1,  3, -1,  3, -1,  1,  3,  1, -1,  3,  1,  3, -3, -3,  1, -1, -1,  1,  3}};
-
 namespace {
 
-__device__ __forceinline__ float2 cmulf(float2 a, float2 b) {
-  return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 mulj(float2 a) { return make_float2(-a.y, a.x); }
-
-// unnormalised inverse DFTs of 2, 3 and 4 points in registers (exp(+j ...))
+// unnormalised inverse DFT of 2 points in registers (exp(+j ...)), beside the shared 3- and 4-point ones
+using mi::idft;
 __device__ __forceinline__ void idft(float2 (&v)[2]) {
   const float2 a = v[0];
   v[0] = cadd(a, v[1]);
   v[1] = csub(a, v[1]);
-}
-__device__ __forceinline__ void idft(float2 (&v)[3]) {
-  const float2 t = cadd(v[1], v[2]), d = csub(v[1], v[2]);
-  const float2 m = make_float2(v[0].x - 0.5f * t.x, v[0].y - 0.5f * t.y);
-  const float h = 0.86602540378443865f;
-  const float2 s = make_float2(-h * d.y, h * d.x);
-  v[0] = cadd(v[0], t);
-  v[1] = cadd(m, s);
-  v[2] = csub(m, s);
-}
-__device__ __forceinline__ void idft(float2 (&v)[4]) {
-  const float2 s0 = cadd(v[0], v[2]), s1 = csub(v[0], v[2]), s2 = cadd(v[1], v[3]), s3 = mulj(csub(v[1], v[3]));
-  v[0] = cadd(s0, s2);
-  v[1] = cadd(s1, s3);
-  v[2] = csub(s0, s2);
-  v[3] = csub(s1, s3);
 }
 
 // one Stockham pass of radix R over the H points of buf, in place, NS = the product of the earlier radices:
@@ -101,7 +45,7 @@ __device__ __forceinline__ void pass(float2* __restrict__ buf, uint32_t H, uint3
       for (uint32_t r = 1; r < R; r++) {
         float s, c;
         sincospif((float)(r * k) * step, &s, &c);   // r k < 3 NS: exact in float
-        v[r] = cmulf(v[r], make_float2(c, s));
+        v[r] = cmul(v[r], make_float2(c, s));
       }
     }
     idft(v);
@@ -138,14 +82,7 @@ __global__ __launch_bounds__(SRS_THREADS) void srs_kernel(const MiSrsTx* __restr
     float2 z = make_float2(0.0f, 0.0f);
     if (n < x.M_sc) {
       const float cs = (float)((x.n_cs * n) % 8u) * 0.25f;
-      float ph;
-      if (x.nzc) {
-        const uint32_t m = n % x.nzc;
-        const uint32_t a = (uint32_t)(((uint64_t)x.q * m * (m + 1)) % (2ull * x.nzc));
-        ph = -(float)a / (float)x.nzc + cs;
-      } else {
-        ph = (float)SRS_PHI24[x.q][n] * 0.25f + cs;
-      }
+      const float ph = base_seq_phase(x.nzc, x.q, x.M_sc, n, [cs] { return cs; });
       float sv, cv;
       sincospif(ph, &sv, &cv);
       z = make_float2(cv, sv);
@@ -173,14 +110,7 @@ __global__ __launch_bounds__(SRS_THREADS) void srs_kernel(const MiSrsTx* __restr
   for (uint32_t i = t; i < N + cp; i += SRS_THREADS) {
     const int n = (int)i - (int)cp;
     const uint32_t nm = (uint32_t)(n + (int)N) % H;
-    // exp(j pi (2 K + 1) n / N), its argument reduced exactly in integers (|(2 K + 1) n| < 2^23), times the
-    // frequency shift (cfo subcarriers over the subframe's sample index)
-    int r = (K2 * n) % twoN;
-    r = r < 0 ? r + twoN : r;
-    float sv, cv;
-    sincospif(((float)r + 2.0f * f * (float)(pos + i)) * rN, &sv, &cv);
-    const float2 y = cmulf(buf[nm], make_float2(cv, sv));
-    dst[pos + i] = make_float2(y.x * gN, y.y * gN);
+    dst[pos + i] = sc_shift_out(buf[nm], K2, n, twoN, f, pos + i, rN, gN);
   }
 }
 

@@ -1,4 +1,4 @@
-// srs_engine.h -- device table + launch of one SRS plan (shared by the batched ABI, srs_batch.cpp, and the
+// srs_engine.h -- device table + launch of one SRS plan (shared by the batched ABI, ul_ctrl_batch.cpp, and the
 // per-TTI mi_ue_ul_srs_encode, ue_ul.cpp).
 #pragma once
 #include "engine.h"

@@ -4,8 +4,7 @@
 #include "srs.h"
 
 #include "plan.h"     // set_error
-#include "tables.h"   // gold_bits
-#include "ul_plan.h"  // ul_base_seq
+#include "ul_plan.h"  // ul_base_seq, ul_group_u, ul_seq_hop_bit
 
 namespace mi {
 namespace {
@@ -19,26 +18,9 @@ const uint8_t M_SRS[4][4][8] = {
 
 uint32_t bw_table(uint32_t nof_prb) { return nof_prb <= 40 ? 0 : nof_prb <= 60 ? 1 : nof_prb <= 80 ? 2 : 3; }
 
-// f_gh(ns) of every slot of the frame (5.5.1.3: c_init = floor(N_ID^cell / 30)); depends on the cell alone
-struct CellGh {
-  uint32_t cell_id = 0xFFFFFFFFu;
-  uint8_t fgh[20];
-  void load(uint32_t id) {
-    if (id == cell_id) return;
-    uint8_t g[160];
-    gold_bits(id / 30, 160, g);
-    for (uint32_t ns = 0; ns < 20; ns++) {
-      uint32_t f = 0;
-      for (uint32_t i = 0; i < 8; i++) f += (uint32_t)g[8 * ns + i] << i;
-      fgh[ns] = (uint8_t)(f % 30);
-    }
-    cell_id = id;
-  }
-};
-
 // every field of c; false + set_error
 bool check(const mi_srs_cfg_t& c) {
-  if (c.nof_prb != 6 && c.nof_prb != 15 && c.nof_prb != 25 && c.nof_prb != 50 && c.nof_prb != 75 && c.nof_prb != 100) {
+  if (!std_nof_prb(c.nof_prb)) {
     set_error("SRS: nof_prb must be one of 6, 15, 25, 50, 75, 100");
     return false;
   }
@@ -66,7 +48,7 @@ bool check(const mi_srs_cfg_t& c) {
   return true;
 }
 
-void derive(const mi_srs_cfg_t& c, CellGh& gh, mi_srs_res_t* r) {
+void derive(const mi_srs_cfg_t& c, mi_srs_res_t* r) {
   uint32_t m[4], Nb[4], T, off;
   for (uint32_t b = 0; b < 4; b++) {
     m[b] = M_SRS[bw_table(c.nof_prb)][b][c.bw_cfg];
@@ -100,20 +82,13 @@ void derive(const mi_srs_cfg_t& c, CellGh& gh, mi_srs_res_t* r) {
   r->T_srs = T;
   // 5.5.1.3: the PUCCH sequence-shift pattern f_ss = N_ID mod 30; 5.5.1.4: c_init uses the PUSCH one
   const uint32_t ns = 2 * (c.tti % 10) + 1;
-  gh.load(c.cell_id);
-  r->u = ((c.group_hopping ? gh.fgh[ns] : 0u) + c.cell_id % 30) % 30;
+  r->u = ul_group_u(c.cell_id, ns, c.group_hopping, c.cell_id % 30);
   r->v = 0;
-  if (c.sequence_hopping && !c.group_hopping && r->M_sc >= 72) {
-    uint8_t s[20];
-    gold_bits((c.cell_id / 30) * 32 + (c.cell_id % 30 + c.delta_ss) % 30, 20, s);
-    r->v = s[ns];
-  }
+  if (c.sequence_hopping && !c.group_hopping && r->M_sc >= 72)
+    r->v = ul_seq_hop_bit(c.cell_id, (c.cell_id % 30 + c.delta_ss) % 30, ns);
   ul_base_seq(r->M_sc, r->u, r->v, &r->q, &r->nzc);
   r->n_cs = c.n_srs;
 }
-
-// srsUE's workers stay on one cell: the sequence is derived once per thread and cell
-thread_local CellGh g_cell;
 
 }  // namespace
 
@@ -126,7 +101,7 @@ int SrsPlan::build(const mi_srs_cfg_t* cfgs, uint32_t n) {
   for (uint32_t i = 0; i < n; i++) {
     const mi_srs_cfg_t& c = cfgs[i];
     mi_srs_res_t r;
-    derive(c, g_cell, &r);
+    derive(c, &r);
     MiSrsTx t{};
     t.N = (uint32_t)symbol_sz(c.nof_prb);
     t.M_sc = r.M_sc;
@@ -152,7 +127,7 @@ uint32_t mi_srs_resource_n(const mi_srs_cfg_t* c, uint32_t n, mi_srs_res_t* r) {
   if (!c || !r) { mi::set_error("SRS: null argument"); return 0; }
   for (uint32_t i = 0; i < n; i++) {
     if (!mi::check(c[i])) return i;
-    mi::derive(c[i], mi::g_cell, &r[i]);
+    mi::derive(c[i], &r[i]);
   }
   return n;
 }

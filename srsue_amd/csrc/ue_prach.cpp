@@ -43,10 +43,9 @@ int mi_prach_init(srslte_prach_t* p, uint32_t N_ifft_ul, uint32_t preamble_forma
                   bool high_speed_flag, uint32_t zero_corr_zone_config) {
   if (!p) return SRSLTE_ERROR_INVALID_INPUTS;
   p->impl = nullptr;
-  static const uint32_t PRB[6] = {6, 15, 25, 50, 75, 100};
   uint32_t nof_prb = 0;
-  for (uint32_t b : PRB)
-    if ((uint32_t)mi::symbol_sz(b) == N_ifft_ul) nof_prb = b;
+  for (uint32_t b = 6; b <= 100; b++)
+    if (mi::std_nof_prb(b) && (uint32_t)mi::symbol_sz(b) == N_ifft_ul) nof_prb = b;
   if (!nof_prb) { mi::set_error("PRACH: N_ifft_ul must be the symbol size of 6, 15, 25, 50, 75 or 100 PRB"); return SRSLTE_ERROR; }
   if (preamble_format > 3) { mi::set_error("PRACH: preamble formats 0-3 only (FDD)"); return SRSLTE_ERROR; }
   // the whole configuration is checked on the host (preamble 0, offset 0) before anything touches the device

@@ -75,6 +75,14 @@ struct mi_ue_ul_ctx {
     if (h_uci) (void)hipHostFree(h_uci);
     if (st) (void)hipStreamDestroy(st);
   }
+  // the subframe (n samples) from d_iq to the caller's buffer; `what` names the stream sync in an error
+  int fetch(size_t n, cf_t* signal, const char* what) {
+    if (!mi::hip_ok(hipMemcpyAsync(h_iq, d_iq.p, n * 8, hipMemcpyDeviceToHost, st), "D2H IQ") ||
+        !mi::hip_ok(hipStreamSynchronize(st), what))
+      return SRSLTE_ERROR;
+    memcpy(signal, h_iq, n * 8);
+    return SRSLTE_SUCCESS;
+  }
 };
 
 namespace {
@@ -341,10 +349,7 @@ int srslte_ue_ul_pusch_encode_rnti_softbuffer(srslte_ue_ul_t* q, uint8_t* data, 
   c->prof.mark(2, c->st);
   if (c->eng.run(src, c->d_iq.p, c->st)) return SRSLTE_ERROR;
   c->prof.mark(3, c->st);
-  if (!mi::hip_ok(hipMemcpyAsync(c->h_iq, c->d_iq.p, n * 8, hipMemcpyDeviceToHost, c->st), "D2H IQ") ||
-      !mi::hip_ok(hipStreamSynchronize(c->st), "ul sync"))
-    return SRSLTE_ERROR;
-  memcpy(output_signal, c->h_iq, n * 8);
+  if (c->fetch(n, output_signal, "ul sync")) return SRSLTE_ERROR;
   c->prof.mark(4, c->st);
   return SRSLTE_SUCCESS;
 }
@@ -388,10 +393,8 @@ int mi_ue_ul_pucch_encode(srslte_ue_ul_t* q, srslte_uci_data_t uci, uint32_t pdc
   const size_t n = (size_t)15 * mi::symbol_sz(q->cell.nof_prb);
   if (!mi::hip_ok(hipMemcpyAsync(c->d_uci.p, c->h_uci, sizeof(uint32_t), hipMemcpyHostToDevice, c->st), "H2D UCI") ||
       c->pucch.upload(c->st) || c->pucch.run(c->d_uci.as<uint32_t>(), c->d_iq.p, c->st) ||
-      !mi::hip_ok(hipMemcpyAsync(c->h_iq, c->d_iq.p, n * 8, hipMemcpyDeviceToHost, c->st), "D2H IQ") ||
-      !mi::hip_ok(hipStreamSynchronize(c->st), "pucch sync"))
+      c->fetch(n, output_signal, "pucch sync"))
     return SRSLTE_ERROR;
-  memcpy(output_signal, c->h_iq, n * 8);
   q->last_pucch_format = (uint32_t)format;
   q->pucch.shortened = p.shortened != 0;
   return SRSLTE_SUCCESS;
@@ -431,12 +434,8 @@ int mi_ue_ul_srs_encode(srslte_ue_ul_t* q, uint32_t tti, cf_t* output_signal) {
   if (q->normalize_en) t.scale = (float)q->cell.nof_prb / 15.0f / sqrtf((float)c->srs.plan.res[0].m_srs / 2.0f);
   if (q->cfo_en) t.cfo = q->current_cfo;
   const size_t n = (size_t)15 * mi::symbol_sz(q->cell.nof_prb);
-  if (c->srs.upload(c->st) || c->srs.run(nullptr, nullptr, c->d_iq.p, c->st) ||
-      !mi::hip_ok(hipMemcpyAsync(c->h_iq, c->d_iq.p, n * 8, hipMemcpyDeviceToHost, c->st), "D2H IQ") ||
-      !mi::hip_ok(hipStreamSynchronize(c->st), "srs sync"))
-    return SRSLTE_ERROR;
-  memcpy(output_signal, c->h_iq, n * 8);
-  return SRSLTE_SUCCESS;
+  if (c->srs.upload(c->st) || c->srs.run(nullptr, nullptr, c->d_iq.p, c->st)) return SRSLTE_ERROR;
+  return c->fetch(n, output_signal, "srs sync");
 }
 
 // Open-loop UL power control (36.213 5.1, ul_power.cpp) with srsUE's argument lists (phch_worker.cc:568, :622, :652)

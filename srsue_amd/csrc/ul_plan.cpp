@@ -21,24 +21,67 @@ static bool prime(uint32_t n) {
   return true;
 }
 
+namespace {
+
+// what 5.5.1.3 / 5.5.1.4 / 5.5.2.1.1 take from Gold sequences, for every slot of the frame: f_gh(ns) of c_init =
+// floor(N_ID / 30), and c(ns) and n_PRS(ns) of c_init = floor(N_ID / 30) 2^5 + f_ss^PUSCH; reloaded when c_init changes
+struct CellHop {
+  bool have_gh = false, have_sh = false;
+  uint32_t gh_init = 0, sh_init = 0;
+  uint8_t fgh[20], c[20], prs[20];
+  void load_gh(uint32_t init) {
+    if (have_gh && init == gh_init) return;
+    uint8_t g[8 * 20];
+    gold_bits(init, sizeof(g), g);
+    for (uint32_t ns = 0; ns < 20; ns++) {
+      uint32_t f = 0;
+      for (uint32_t i = 0; i < 8; i++) f += (uint32_t)g[8 * ns + i] << i;
+      fgh[ns] = (uint8_t)(f % 30);
+    }
+    gh_init = init;
+    have_gh = true;
+  }
+  void load_sh(uint32_t init) {
+    if (have_sh && init == sh_init) return;
+    uint8_t s[8 * 7 * 20];
+    gold_bits(init, sizeof(s), s);
+    for (uint32_t ns = 0; ns < 20; ns++) {
+      uint32_t p = 0;
+      for (uint32_t i = 0; i < 8; i++) p += (uint32_t)s[8 * 7 * ns + i] << i;
+      c[ns] = s[ns];
+      prs[ns] = (uint8_t)p;
+    }
+    sh_init = init;
+    have_sh = true;
+  }
+};
+// srsUE's workers stay on one cell and run concurrently: derived once per thread and cell
+thread_local CellHop g_hop;
+
+}  // namespace
+
+uint32_t ul_group_u(uint32_t cell_id, uint32_t ns, bool group_hopping, uint32_t fss) {
+  uint32_t fgh = 0;
+  if (group_hopping) {
+    g_hop.load_gh(cell_id / 30);
+    fgh = g_hop.fgh[ns];
+  }
+  return (fgh + fss) % 30;
+}
+
+uint32_t ul_seq_hop_bit(uint32_t cell_id, uint32_t fss_pusch, uint32_t ns) {
+  g_hop.load_sh((cell_id / 30) * 32 + fss_pusch);
+  return g_hop.c[ns];
+}
+
 int ul_dmrs_params(const mi_ul_cfg_t& c, uint32_t ns, uint32_t* q, uint32_t* nzc, uint32_t* ncs) {
   const uint32_t M = 12 * c.L_prb, fss = (c.cell_id + c.delta_ss) % 30;
   if (M < 12 || ns >= 20) return -1;
-  uint32_t fgh = 0;
-  if (c.group_hopping) {               // 5.5.1.3: c_init = floor(N_ID / 30)
-    std::vector<uint8_t> g(160);
-    gold_bits(c.cell_id / 30, 160, g.data());
-    for (int i = 0; i < 8; i++) fgh += (uint32_t)g[8 * ns + i] << i;
-    fgh %= 30;
-  }
-  const uint32_t u = (fgh + fss) % 30;
+  const uint32_t u = ul_group_u(c.cell_id, ns, c.group_hopping, fss);
   // sequence hopping (5.5.1.4) and n_PRS (5.5.2.1.1) share c_init = floor(N_ID / 30) 2^5 + f_ss
-  std::vector<uint8_t> s(8 * 7 * 20);
-  gold_bits((c.cell_id / 30) * 32 + fss, 8 * 7 * 20, s.data());
-  const uint32_t v = (M >= 72 && !c.group_hopping && c.sequence_hopping) ? s[ns] : 0;
-  uint32_t prs = 0;
-  for (int i = 0; i < 8; i++) prs += (uint32_t)s[8 * 7 * ns + i] << i;
-  *ncs = (N1_DMRS[c.cyclic_shift & 7] + N2_DMRS[c.n_dmrs2 & 7] + prs) % 12;
+  const uint32_t hop = ul_seq_hop_bit(c.cell_id, fss, ns);
+  const uint32_t v = (M >= 72 && !c.group_hopping && c.sequence_hopping) ? hop : 0;
+  *ncs = (N1_DMRS[c.cyclic_shift & 7] + N2_DMRS[c.n_dmrs2 & 7] + g_hop.prs[ns]) % 12;
   ul_base_seq(M, u, v, q, nzc);
   return 0;
 }

@@ -14,6 +14,12 @@ namespace mi {
 
 // 36.211 5.5.2.1 / 5.5.1: DMRS root q, Zadoff-Chu length and cyclic shift of slot ns (0..19)
 int ul_dmrs_params(const mi_ul_cfg_t& c, uint32_t ns, uint32_t* q, uint32_t* nzc, uint32_t* ncs);
+// 36.211 5.5.1.3: sequence-group number u = (f_gh(ns) [with group hopping] + f_ss) mod 30 of slot ns (0..19).  f_ss is
+// the caller's: (N_ID + delta_ss) mod 30 for the PUSCH, N_ID mod 30 for the PUCCH and the SRS.  f_gh of the whole
+// frame is kept per thread and cell
+uint32_t ul_group_u(uint32_t cell_id, uint32_t ns, bool group_hopping, uint32_t fss);
+// 36.211 5.5.1.4: the sequence-hopping bit c(ns), c_init = floor(N_ID / 30) 2^5 + f_ss^PUSCH, kept likewise
+uint32_t ul_seq_hop_bit(uint32_t cell_id, uint32_t fss_pusch, uint32_t ns);
 // 36.211 5.5.1.1 / 5.5.1.2: root q and Zadoff-Chu length of the base sequence r_{u,v} of length M (a multiple of
 // 12); M < 36: the tabulated sequences, nzc = 0 and q = u.  Shared by the PUSCH DMRS and the SRS (srs_host.cpp)
 void ul_base_seq(uint32_t M, uint32_t u, uint32_t v, uint32_t* q, uint32_t* nzc);

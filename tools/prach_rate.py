@@ -10,38 +10,15 @@ and the wall time of init + 64 x gen on a fresh instance.
 Warm-up, then repeated timed calls; reports the median and the spread (min .. max).  There is no earlier path to
 compare with: the figures are a record."""
 import argparse
-import json
-import os
 import struct
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from srsue_amd import abi  # noqa: E402
+from rate_common import need_gpu, report, run_harness, timed   # puts the repository root on sys.path
+from srsue_amd import abi
 
-HARNESS = os.path.join(ROOT, "tests", "c", "ue_prach_harness")
 CELL = dict(root_seq_idx=22, zero_corr_zone=12, high_speed=0)   # N_CS = 119: 7 shifts per root, 10 roots
-
-
-def timed(fn, warmup, repeats):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    ms = np.sort(np.asarray(ms))
-    return float(np.median(ms)), float(ms[0]), float(ms[-1])
 
 
 def batch_rate(nof_prb, config_idx, flags, warmup, repeats):
@@ -50,8 +27,9 @@ def batch_rate(nof_prb, config_idx, flags, warmup, repeats):
     b = abi.PrachBatch(cfgs, flags=flags)
     d_iq = torch.zeros(2 * b.iq_samples, dtype=torch.float32, device="cuda")
     st = torch.cuda.current_stream().cuda_stream
-    med, lo, hi = timed(lambda: b.run(d_iq.data_ptr(), st), warmup, repeats)
-    fill, _, _ = timed(lambda: d_iq.fill_(1.0), warmup, repeats)
+    ms = timed(lambda: b.run(d_iq.data_ptr(), st), warmup, repeats)
+    med, lo, hi = float(np.median(ms)), float(ms[0]), float(ms[-1])
+    fill = float(np.median(timed(lambda: d_iq.fill_(1.0), warmup, repeats)))
     gb = 8 * b.iq_samples / 1e9
     out = {"nof_prb": nof_prb, "format": config_idx // 16, "single_residue": bool(flags), "preambles": 64,
            "iq_mbytes": gb * 1e3, "median_ms": med, "min_ms": lo, "max_ms": hi, "preambles_per_s": 64 / (med * 1e-3),
@@ -62,14 +40,9 @@ def batch_rate(nof_prb, config_idx, flags, warmup, repeats):
 
 
 def per_call(nof_prb, config_idx, repeats):
-    with tempfile.TemporaryDirectory() as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(struct.pack("8i", nof_prb, config_idx, CELL["root_seq_idx"], CELL["high_speed"],
-                                CELL["zero_corr_zone"], (nof_prb - 6) // 2, 5, 0))
-            f.write(struct.pack("2f", 0.3, 0.5))
-        line = subprocess.check_output([HARNESS, fin, fout, str(repeats)], timeout=300).decode().strip().splitlines()[-1]
-    return dict(json.loads(line), nof_prb=nof_prb, format=config_idx // 16)
+    rec = struct.pack("8i", nof_prb, config_idx, CELL["root_seq_idx"], CELL["high_speed"], CELL["zero_corr_zone"],
+                      (nof_prb - 6) // 2, 5, 0) + struct.pack("2f", 0.3, 0.5)
+    return run_harness("ue_prach_harness", rec, repeats, nof_prb=nof_prb, format=config_idx // 16)
 
 
 def main():
@@ -79,18 +52,12 @@ def main():
     ap.add_argument("--call-repeats", type=int, default=200)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("prach_rate.py needs a GPU")
     shapes = [(6, 0), (6, 48), (100, 0), (100, 48)]
-    r = {"device": torch.cuda.get_device_name(0),
+    r = {"device": need_gpu("prach_rate.py"),
          "batch": [batch_rate(prb, c, flags, a.warmup, a.repeats) for prb, c in shapes
                    for flags in (0, abi.PRACH_FLAG_SINGLE_RESIDUE)],
          "per_call": [per_call(prb, c, a.call_repeats) for prb, c in shapes]}
-    line = json.dumps(r)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    report(r, a.out)
 
 
 if __name__ == "__main__":

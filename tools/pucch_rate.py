@@ -7,28 +7,13 @@ download and copy-out).
 Warm-up, then repeated timed calls; reports the median and the spread (min .. max).  There is no earlier path to
 compare with: the figures are a record."""
 import argparse
-import json
-import os
 import struct
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from srsue_amd import abi  # noqa: E402
-
-HARNESS = os.path.join(ROOT, "tests", "c", "ue_pucch_harness")
-
-
-def stats(ms, n):
-    ms = np.sort(np.asarray(ms))
-    return {"median_ms": float(np.median(ms)), "min_ms": float(ms[0]), "max_ms": float(ms[-1]),
-            "per_s_median": float(n / (np.median(ms) * 1e-3)), "per_s_min": float(n / (ms[-1] * 1e-3)),
-            "per_s_max": float(n / (ms[0] * 1e-3))}
+from rate_common import need_gpu, report, run_harness, stats, timed   # puts the repository root on sys.path
+from srsue_amd import abi
 
 
 def batch_rate(n, nof_prb, warmup, repeats):
@@ -44,17 +29,7 @@ def batch_rate(n, nof_prb, warmup, repeats):
     d_uci = torch.from_numpy(words).cuda()
     d_iq = torch.zeros(2 * b.iq_samples, dtype=torch.float32, device="cuda")
     st = torch.cuda.current_stream().cuda_stream
-    for _ in range(warmup):
-        b.run(d_uci.data_ptr(), d_iq.data_ptr(), st)
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        b.run(d_uci.data_ptr(), d_iq.data_ptr(), st)
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
+    ms = timed(lambda: b.run(d_uci.data_ptr(), d_iq.data_ptr(), st), warmup, repeats)
     out = dict(stats(ms, n), transmissions=n, nof_prb=nof_prb, iq_gbytes_per_s=float(8 * b.iq_samples / (np.median(ms) * 1e6)))
     b.close()
     return out
@@ -63,16 +38,10 @@ def batch_rate(n, nof_prb, warmup, repeats):
 def per_tti(nof_prb, repeats):
     """ACK (format 1a), ACK + CQI (format 2a) and SR (format 1), each repeated `repeats` times"""
     calls = [(14, 7, 1, 1, 0, 0), (25, 7, 1, 0, 0, 4), (36, 0, 0, 0, 1, 0)]
-    with tempfile.TemporaryDirectory() as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(struct.pack("16i", 1, nof_prb, len(calls), 0, 0, 1, 0, 1, 0, 0, 0, 11, 3, 29, 0x46, 0))
-            f.write(struct.pack("f", 0.0))
-            for c in calls:
-                f.write(struct.pack("6i", *c))
-                f.write(bytes([1, 0, 1, 1] + [0] * 60))
-        line = subprocess.check_output([HARNESS, fin, fout, str(repeats)], timeout=300).decode().strip().splitlines()[-1]
-    return dict(json.loads(line), nof_prb=nof_prb)
+    rec = struct.pack("16i", 1, nof_prb, len(calls), 0, 0, 1, 0, 1, 0, 0, 0, 11, 3, 29, 0x46, 0) + struct.pack("f", 0.0)
+    for c in calls:
+        rec += struct.pack("6i", *c) + bytes([1, 0, 1, 1] + [0] * 60)
+    return run_harness("ue_pucch_harness", rec, repeats, nof_prb=nof_prb)
 
 
 def main():
@@ -83,16 +52,10 @@ def main():
     ap.add_argument("--tti-repeats", type=int, default=200)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("pucch_rate.py needs a GPU")
-    r = {"device": torch.cuda.get_device_name(0),
+    r = {"device": need_gpu("pucch_rate.py"),
          "batch": [batch_rate(n, prb, a.warmup, a.repeats) for prb in (6, 100) for n in a.batches],
          "per_tti": [per_tti(prb, a.tti_repeats) for prb in (6, 100)]}
-    line = json.dumps(r)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    report(r, a.out)
 
 
 if __name__ == "__main__":

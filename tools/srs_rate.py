@@ -8,31 +8,17 @@ from tests/c/ue_pucch_harness in the same run.
 Warm-up, then repeated timed calls; reports the median and the spread (min .. max).  There is no earlier path to
 compare with: the figures are a record."""
 import argparse
-import json
-import os
 import struct
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from srsue_amd import abi  # noqa: E402
+from pucch_rate import per_tti as per_tti_pucch
+from rate_common import need_gpu, report, run_harness, stats, timed   # puts the repository root on sys.path
+from srsue_amd import abi
 
-HARNESS = os.path.join(ROOT, "tests", "c", "ue_srs_harness")
-PUCCH_HARNESS = os.path.join(ROOT, "tests", "c", "ue_pucch_harness")
 # (bw_cfg, B) that every transmission of a bandwidth cycles through: 6 PRB admits only C_SRS 7
 SHAPES = {6: [(7, 0)], 100: [(0, 0), (0, 1), (0, 2), (0, 3), (2, 0), (5, 1), (7, 0), (7, 3)]}
-
-
-def stats(ms, n):
-    ms = np.sort(np.asarray(ms))
-    return {"median_ms": float(np.median(ms)), "min_ms": float(ms[0]), "max_ms": float(ms[-1]),
-            "per_s_median": float(n / (np.median(ms) * 1e-3)), "per_s_min": float(n / (ms[-1] * 1e-3)),
-            "per_s_max": float(n / (ms[0] * 1e-3))}
 
 
 def batch_rate(n, nof_prb, flags, warmup, repeats):
@@ -44,17 +30,7 @@ def batch_rate(n, nof_prb, flags, warmup, repeats):
     b = abi.SrsBatch(cfgs, flags=flags)
     d_iq = torch.zeros(2 * b.iq_samples, dtype=torch.float32, device="cuda")
     st = torch.cuda.current_stream().cuda_stream
-    for _ in range(warmup):
-        b.run(d_iq.data_ptr(), st)
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        b.run(d_iq.data_ptr(), st)
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
+    ms = timed(lambda: b.run(d_iq.data_ptr(), st), warmup, repeats)
     N = 2048 if nof_prb == 100 else 128
     written = (N + 144 * N // 2048) * n if flags else b.iq_samples
     out = dict(stats(ms, n), transmissions=n, nof_prb=nof_prb, last_symbol_only=bool(flags),
@@ -67,29 +43,9 @@ def per_tti(nof_prb, repeats):
     """three SRS instants of a hopping configuration, each repeated `repeats` times"""
     bw_cfg, B = (7, 0) if nof_prb == 6 else (0, 1)
     ttis = [2, 12, 22]
-    with tempfile.TemporaryDirectory() as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(struct.pack("20i", 1, nof_prb, len(ttis), 0, 0, 0, 0, 1, 0, bw_cfg, 9, B, 0, 5, 0, 3, 0, 0x46, 0, 0))
-            f.write(struct.pack("16f", *([0.0] * 16)))
-            f.write(struct.pack(f"{len(ttis)}i", *ttis))
-        line = subprocess.check_output([HARNESS, fin, fout, str(repeats)], timeout=300).decode().strip().splitlines()[-1]
-    return dict(json.loads(line), nof_prb=nof_prb)
-
-
-def per_tti_pucch(nof_prb, repeats):
-    """the per-TTI PUCCH call (format 1a, format 2a, format 1) on the same machine in the same run, for comparison"""
-    calls = [(14, 7, 1, 1, 0, 0), (25, 7, 1, 0, 0, 4), (36, 0, 0, 0, 1, 0)]
-    with tempfile.TemporaryDirectory() as d:
-        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-        with open(fin, "wb") as f:
-            f.write(struct.pack("16i", 1, nof_prb, len(calls), 0, 0, 1, 0, 1, 0, 0, 0, 11, 3, 29, 0x46, 0))
-            f.write(struct.pack("f", 0.0))
-            for c in calls:
-                f.write(struct.pack("6i", *c))
-                f.write(bytes([1, 0, 1, 1] + [0] * 60))
-        line = subprocess.check_output([PUCCH_HARNESS, fin, fout, str(repeats)], timeout=300).decode().strip().splitlines()[-1]
-    return dict(json.loads(line), nof_prb=nof_prb)
+    rec = struct.pack("20i", 1, nof_prb, len(ttis), 0, 0, 0, 0, 1, 0, bw_cfg, 9, B, 0, 5, 0, 3, 0, 0x46, 0, 0)
+    rec += struct.pack("16f", *([0.0] * 16)) + struct.pack(f"{len(ttis)}i", *ttis)
+    return run_harness("ue_srs_harness", rec, repeats, nof_prb=nof_prb)
 
 
 def main():
@@ -100,17 +56,11 @@ def main():
     ap.add_argument("--tti-repeats", type=int, default=200)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("srs_rate.py needs a GPU")
-    r = {"device": torch.cuda.get_device_name(0),
+    r = {"device": need_gpu("srs_rate.py"),
          "batch": [batch_rate(n, prb, fl, a.warmup, a.repeats) for prb in (6, 100) for fl in (0, 1) for n in a.batches],
          "per_tti": [per_tti(prb, a.tti_repeats) for prb in (6, 100)],
          "per_tti_pucch": [per_tti_pucch(prb, a.tti_repeats) for prb in (6, 100)]}
-    line = json.dumps(r)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    report(r, a.out)
 
 
 if __name__ == "__main__":
