@@ -3,7 +3,10 @@
 // never linked into the product library.  Lanes of those kernels never communicate, so running
 // each lane's code to completion in turn reproduces the GPU result operation for operation; the
 // CPU test suite uses it to check planner + rate de-matching + turbo + TB assembly bit-exactly
-// against the oracle without a GPU.
+// against the oracle without a GPU.  The per-work-item setup -- what turns (group or pair, lane) into a TdecArgs /
+// TdecArgsP2, the output routing, the result write-back and the gather sources -- is not restated here: it is the
+// MI_HD functions of tdec_body.h / tdec_p2_body.h that tdec.hip's kernels call, run on host arrays laid out as the
+// device buffers are (one window-mask array of WM_STRIDE per group, dense pairs a fixed stride apart).
 #include <algorithm>
 #include <string.h>
 
@@ -113,20 +116,9 @@ static mi::TdecLaneResult emu_win_cb(const MiGroupDesc& g, const MiKTab& kt, con
   return r;
 }
 
-// the packed decoder writes each code block's payload run in place (tdec.hip p2_out)
-static void emu_p2_out(mi::TdecArgsP2& a, int h, uint8_t* payload, const MiLaneDesc& ld) {
-  a.out_bytes = payload;
-  a.cb_off[h] = ld.pay_st;
-  a.crc24a[h] = ld.crc24a | (ld.tbcrc << 1);
-  a.to_payload = 1;
-}
-
 extern "C" int emu_decode_llr(const mi_dl_sf_cfg_t* cfgs, uint32_t n, const float* llr_concat, uint32_t max_its,
                               uint8_t* payload, uint32_t* tb_ok, uint32_t* tb_its, uint32_t* cb_its) {
-  for (uint32_t b = 0; b < 256; b++) {
-    crc8[b] = mi::crc24_byte_entry(b, mi::CRC24A_POLY);
-    crc8b[b] = mi::crc24_byte_entry(b, mi::CRC24B_POLY);
-  }
+  mi::crc24_fill_tables(crc8, crc8b, 0, 1);
   mi::Plan P;
   if (P.build(cfgs, n, true)) return -1;
   std::vector<float> e(P.e_floats, 0.f), sb(P.sb_floats, 0.f), scr(P.scratch_floats, 0.f);
@@ -138,60 +130,41 @@ extern "C" int emu_decode_llr(const mi_dl_sf_cfg_t* cfgs, uint32_t n, const floa
     memcpy(&e[P.sfs[s].e_off], llr_concat + src, G * sizeof(float));
     src += G;
   }
-  if (g_x == 3 && g_q16) {
-    // two code blocks per lane (tdec_p2_body.h): rate de-matching of every group, then the group pairs
-    std::vector<std::vector<uint32_t>> wms(P.groups.size());
-    for (size_t gi = 0; gi < P.groups.size(); gi++) {
-      const MiGroupDesc& g = P.groups[gi];
-      float* sbg = &sb[g.sb_off];
-      uint8_t* map = reinterpret_cast<uint8_t*>(sbg + mi::sb_map_off(g.Ncb));
-      for (uint32_t p = 0; p < g.Ncb; p++) mi::rm_combine_row(&P.lanes[g.lane0], P.kdata.data(), e.data(), sbg, g.Ncb, p,
-                                                              &P.kdata[P.ktabs[g.ktab].ipos_off]);
-      const MiKTab& kt = P.ktabs[g.ktab];
-      wms[gi].resize(g.K / mi::BETA_W + 1);
-      for (uint32_t w = 0; w < wms[gi].size(); w++) wms[gi][w] = mi::tdec_window_mask(map, &P.kdata[kt.pos_off], w);
-    }
+  // rate de-matching and the window masks of every group (rm.hip, tdec.hip rowmask_kernel), then the decoders on the
+  // buffers and tables laid out as the kernels get them
+  std::vector<uint32_t> wm(P.groups.size() * mi::WM_STRIDE, 0u);
+  for (size_t gi = 0; gi < P.groups.size(); gi++) {
+    const MiGroupDesc& g = P.groups[gi];
+    float* sbg = &sb[g.sb_off];
+    const uint8_t* map = reinterpret_cast<const uint8_t*>(sbg + mi::sb_map_off(g.Ncb));
+    const MiKTab& kt = P.ktabs[g.ktab];
+    for (uint32_t p = 0; p < g.Ncb; p++)
+      mi::rm_combine_row(&P.lanes[g.lane0], P.kdata.data(), e.data(), sbg, g.Ncb, p, &P.kdata[kt.ipos_off]);
+    for (uint32_t w = 0; w <= g.K / mi::BETA_W; w++)
+      wm[gi * mi::WM_STRIDE + w] = mi::tdec_window_mask(map, &P.kdata[kt.pos_off], w);
+  }
+  const bool p2 = g_x == 3 && g_q16;   // two code blocks per lane (tdec_p2_body.h): its runs go to the payload in place
+  const mi::TdecMem m{sb.data(), wm.data(), scr.data(), dec.data(), cbb.data(), p2 ? payload : nullptr, P.kdata.data()};
+  if (p2) {
     std::vector<uint32_t> stash((size_t)mi::P2_STASH_ROWS * mi::LANES);
+    const uint32_t its1 = g_compact && max_its > 1 ? 1 : max_its;   // tdec.hip launch_tdec_p2, as Engine::launch_turbo
     for (size_t pp = 0; pp < P.pairs.size(); pp += 2) {
       const uint32_t ga = P.pairs[pp], gbi = P.pairs[pp + 1];
-      const bool paired = gbi != 0xFFFFFFFFu;
-      const uint32_t gb = paired ? gbi : ga;
-      const MiGroupDesc &gA = P.groups[ga], &gB = P.groups[gb];
-      const MiKTab& kt = P.ktabs[gA.ktab];
+      const MiGroupDesc &gA = P.groups[ga], &gB = P.groups[gbi != 0xFFFFFFFFu ? gbi : ga];
       for (int lane = 0; lane < mi::LANES; lane++) {
         const uint32_t li[2] = {gA.lane0 + lane, gB.lane0 + lane};
         const MiLaneDesc &l0 = P.lanes[li[0]], &l1 = P.lanes[li[1]];
         mi::TdecArgsP2 a;
-        a.live = (l0.valid ? 1u : 0u) | (paired && l1.valid ? 2u : 0u);
+        a.live = mi::p2_first_live(gbi, l0, l1);
         if (!a.live) continue;
-        a.sb[0] = &sb[gA.sb_off]; a.sb[1] = &sb[gB.sb_off];
+        mi::p2_first_args(a, m, ga, gbi, gA, gB, P.ktabs[gA.ktab], li, l0, l1, crc8, crc8b, its1, 1,
+                          its1 == 1 && !g_store_w);
         a.stash = stash.data();   // the LDS stash of the 16-step spans (one lane at a time here)
-        a.wm[0] = wms[ga].data(); a.wm[1] = wms[gb].data();
-        a.zrow[0] = gA.Ncb; a.zrow[1] = gB.Ncb;
-        a.scr = reinterpret_cast<uint32_t*>(&scr[gA.scratch_off]);
-        a.q = a.scr + (size_t)(4 * gA.K + 8) * mi::LANES;
-        a.pos = &P.kdata[kt.pos_off]; a.pi = &P.kdata[kt.pi_off];
-        a.crc8 = crc8;
-        a.crc8b = crc8b;
-        a.dec = &dec[gA.dec_off];
-        for (int h = 0; h < 2; h++) emu_p2_out(a, h, payload, P.lanes[li[(a.live >> h) & 1u ? h : 0]]);
-        a.K = gA.K;
-        a.F[0] = l0.F; a.F[1] = paired ? l1.F : l0.F;
-
-        a.max_its = g_compact && max_its > 1 ? 1 : max_its; a.early_stop = 1;
-        a.cont_w = 0;
-        a.no_w = a.max_its == 1 && !g_store_w;   // tdec.hip launch_tdec_p2
         mi::TdecP2ExecHost ex;
         // the spacing of tdec.hip tdec_kernel_p2x: 16-step spans
-        const mi::TdecP2Result r = a.max_its == 1  ? mi::tdec_p2_lane<false, mi::P2_CKS, true>(a, lane, ex)
-                                   : !a.early_stop ? mi::tdec_p2_lane<false, mi::P2_CKS, false, 0u>(a, lane, ex)
-                                                   : mi::tdec_p2_lane<false, mi::P2_CKS>(a, lane, ex);
-        for (int h = 0; h < 2; h++) {
-          if (!((a.live >> h) & 1u)) continue;
-          cits[li[h]] = r.its[h];
-          ccrc[li[h]] = r.crc_ok[h];
-          ctbp[li[h]] = r.tb_part[h];
-        }
+        const mi::TdecP2Result r = its1 == 1 ? mi::tdec_p2_lane<false, mi::P2_CKS, true>(a, lane, ex)
+                                             : mi::tdec_p2_lane<false, mi::P2_CKS>(a, lane, ex);
+        mi::p2_put_result(a.live, li, r, cits.data(), ccrc.data(), ctbp.data());
       }
     }
     if (g_compact && max_its > 1) {
@@ -216,24 +189,30 @@ extern "C" int emu_decode_llr(const mi_dl_sf_cfg_t* cfgs, uint32_t n, const floa
         const MiKTab& kt = P.ktabs[P.groups[gi0].ktab];
         const uint32_t* pos = &P.kdata[kt.pos_off];
         const size_t PU = (size_t)(7 * K + 20) * mi::LANES;   // tdec.hip: a dense continuation pair
-        const size_t np1 = (cont.size() + 2 * mi::LANES - 1) / (2 * mi::LANES);
-        std::vector<std::vector<uint32_t>> bufs(np1, std::vector<uint32_t>(PU, 0u));
+        auto npairs = [](size_t cbs) { return (cbs + 2 * mi::LANES - 1) / (2 * mi::LANES); };
+        // the live halves of lane `lane` of dense pair p of a list of cbs code blocks, and each one's slot
+        auto slots = [](size_t cbs, size_t p, int lane, size_t (&d)[2]) {
+          uint32_t live = 0;
+          for (int h = 0; h < 2; h++) {
+            d[h] = p * 2 * mi::LANES + (size_t)h * mi::LANES + lane;
+            if (d[h] < cbs) live |= 1u << h;
+          }
+          return live;
+        };
+        std::vector<uint32_t> bufs(npairs(cont.size()) * PU, 0u);   // dense pair p at p PU
         // round 1's gather (tdec_cont_gather_kernel): q rows from the softbuffer, w or x2 rows from the source pairs
-        for (size_t p = 0; p < np1; p++)
+        for (size_t p = 0; p < npairs(cont.size()); p++)
           for (int lane = 0; lane < mi::LANES; lane++) {
-            uint32_t live = 0;
-            mi::P2ContSrc src[2] = {};
-            for (int h = 0; h < 2; h++) {
-              const size_t d = p * 2 * mi::LANES + (size_t)h * mi::LANES + lane;
-              if (d >= cont.size()) continue;
-              const uint32_t li = cont[d];
-              live |= 1u << h;
-              const uint32_t g = li / mi::LANES;
-              src[h] = {&sb[P.groups[g].sb_off], wms[g].data(),
-                        reinterpret_cast<const uint32_t*>(&scr[P.groups[pa[g]].scratch_off]), li % mi::LANES, ph[g]};
-            }
+            size_t d[2];
+            const uint32_t live = slots(cont.size(), p, lane, d);
             if (!live) continue;
-            uint32_t* cscr = bufs[p].data();
+            mi::P2ContSrc src[2] = {};
+            for (int h = 0; h < 2; h++)
+              if ((live >> h) & 1u) {
+                const uint32_t g = cont[d[h]] / mi::LANES;
+                src[h] = mi::p2_cont_src(m.sb, m.wm, m.scratch, P.groups.data(), cont[d[h]], pa[g], ph[g]);
+              }
+            uint32_t* cscr = &bufs[p * PU];
             uint32_t* cq = &cscr[(size_t)(4 * K + 8) * mi::LANES];
             for (uint32_t w = 0; w < mi::p2_cont_qwins(K); w++) {
               uint32_t q[3 * mi::BETA_W];
@@ -245,57 +224,40 @@ extern "C" int emu_decode_llr(const mi_dl_sf_cfg_t* cfgs, uint32_t n, const floa
               else cscr[(size_t)(K + k) * mi::LANES + lane] = mi::p2_cont_xrow(src, live, K, k);
             }
           }
-        // iterations it0 .. it_end - 1 of every dense pair (tdec_kernel_p2c)
+        // iterations it0 .. it_end - 1 of every dense pair (tdec_kernel_p2c, or segmented: tdec_kernel_p2s)
         std::vector<uint32_t> segv((size_t)4 * 64 * mi::P2_CKW * mi::LANES);   // the segmented form's boundary vectors
-        auto run_pairs = [&](std::vector<std::vector<uint32_t>>& pb, const std::vector<uint32_t>& list, uint32_t it0,
+        auto run_pairs = [&](std::vector<uint32_t>& pb, const std::vector<uint32_t>& list, uint32_t it0,
                              uint32_t it_end) {
-          for (size_t p = 0; p < pb.size(); p++) {
-            std::vector<uint8_t> cdec((size_t)K * mi::LANES, 0);
+          const size_t dstride = (size_t)K * mi::LANES;
+          std::vector<uint8_t> cdec(npairs(list.size()) * dstride, 0);
+          std::vector<uint32_t> dl(1, (uint32_t)list.size());   // the device's list: its count, then the lane indices
+          dl.insert(dl.end(), list.begin(), list.end());
+          for (size_t p = 0; p < npairs(list.size()); p++)
             for (int lane = 0; lane < mi::LANES; lane++) {
-              uint32_t li[2] = {0, 0};
               mi::TdecArgsP2 a{};
-              for (int h = 0; h < 2; h++) {
-                const size_t d = p * 2 * mi::LANES + (size_t)h * mi::LANES + lane;
-                if (d < list.size()) { li[h] = list[d]; a.live |= 1u << h; }
-              }
+              uint32_t li[2];
+              // (the segmented kernel's form of the mapping also serves lanes without code blocks: none decoded here)
+              a.live = g_seg && it0 > 1 ? mi::p2_cont_lanes<true>(li, dl.data(), dl[0], (uint32_t)p, lane)
+                                        : mi::p2_cont_lanes<false>(li, dl.data(), dl[0], (uint32_t)p, lane);
               if (!a.live) continue;
-              if (!(a.live & 2u)) li[1] = li[0];
-              a.scr = pb[p].data();
-              a.q = a.scr + (size_t)(4 * K + 8) * mi::LANES;
-              a.pos = pos; a.pi = &P.kdata[kt.pi_off];
-              a.crc8 = crc8; a.crc8b = crc8b;
-              a.dec = cdec.data();
-              for (int h = 0; h < 2; h++) {
-                emu_p2_out(a, h, payload, P.lanes[li[h]]);
-                a.F[h] = P.lanes[li[h]].F;
-              }
-              a.K = K; a.max_its = max_its; a.early_stop = 1;
-              a.cont_w = it0 > 1 || g_store_w;
-              a.it0 = it0; a.it_end = it_end;
+              mi::p2_cont_args(a, li, (uint32_t)p, pb.data(), PU, cdec.data(), dstride, m.cb_bytes, m.payload,
+                               P.lanes.data(), m.kdata, kt, crc8, crc8b, K, max_its, it0 > 1 || g_store_w, it0, it_end);
               mi::TdecP2ExecHost ex;
-              mi::TdecP2Result r{};
+              mi::TdecP2Result r;
               if (g_seg && it0 > 1) {
                 // tdec.hip tdec_kernel_p2s: the segments of one lane in turn, fix-up rounds until nothing changes
                 const size_t vw = (size_t)g_seg * mi::P2_CKW * mi::LANES;
                 mi::P2SegVecs V{&segv[0], &segv[vw], &segv[2 * vw], &segv[3 * vw]};
                 mi::p2s_half_host<false>(a, lane, (uint32_t)g_seg, V);
                 mi::p2s_half_host<true>(a, lane, (uint32_t)g_seg, V);
-                uint32_t tbp[2] = {0u, 0u};
-                const uint32_t ok = mi::tdec_p2_check(a, lane, a.live, tbp);
-                for (int h = 0; h < 2; h++) r.its[h] = it0 + 1, r.crc_ok[h] = (ok >> h) & 1u, r.tb_part[h] = tbp[h];
+                r = mi::p2s_check(a, lane);
               } else {
                 // tdec.hip launch_tdec_cont: 4-step checkpoints in the rounds after the first
                 r = it0 > 1 ? mi::tdec_p2_lane<true, mi::P2C_CKS_LATE>(a, lane, ex)
                             : mi::tdec_p2_lane<true, mi::P2C_CKS>(a, lane, ex);
               }
-              for (int h = 0; h < 2; h++) {
-                if (!((a.live >> h) & 1u)) continue;
-                cits[li[h]] = r.its[h];
-                ccrc[li[h]] = r.crc_ok[h];
-                ctbp[li[h]] = r.tb_part[h];
-              }
+              mi::p2_put_result(a.live, li, r, cits.data(), ccrc.data(), ctbp.data());
             }
-          }
         };
         if (!g_rounds) {
           run_pairs(bufs, cont, 1, max_its);
@@ -309,26 +271,20 @@ extern "C" int emu_decode_llr(const mi_dl_sf_cfg_t* cfgs, uint32_t n, const floa
           for (size_t d = cont.size(); d-- > 0;)
             if (!ccrc[cont[d]]) { next.push_back(cont[d]); srcs.push_back((uint32_t)d); }
           g_round_cbs += next.size();
-          const size_t np = (next.size() + 2 * mi::LANES - 1) / (2 * mi::LANES);
-          std::vector<std::vector<uint32_t>> nb(np, std::vector<uint32_t>(PU, 0u));
-          for (size_t p = 0; p < np; p++)   // tdec_cont_gather2_kernel
+          std::vector<uint32_t> nb(npairs(next.size()) * PU, 0u);
+          for (size_t p = 0; p < npairs(next.size()); p++)   // tdec_cont_gather2_kernel
             for (int lane = 0; lane < mi::LANES; lane++) {
-              uint32_t live = 0;
-              mi::P2ContSrc src[2] = {};
-              for (int h = 0; h < 2; h++) {
-                const size_t d = p * 2 * mi::LANES + (size_t)h * mi::LANES + lane;
-                if (d >= next.size()) continue;
-                const uint32_t e = srcs[d];
-                live |= 1u << h;
-                src[h].scr = bufs[e / (2 * mi::LANES)].data();
-                src[h].ls = e % mi::LANES;
-                src[h].hs = (e / mi::LANES) & 1u;
-              }
+              size_t d[2];
+              const uint32_t live = slots(next.size(), p, lane, d);
               if (!live) continue;
-              for (uint32_t r = 0; r < K; r++) nb[p][(size_t)r * mi::LANES + lane] = mi::p2_cont_drow(src, live, r);
+              mi::P2ContSrc src[2] = {};
+              for (int h = 0; h < 2; h++)
+                if ((live >> h) & 1u) src[h] = mi::p2_cont_src2(bufs.data(), PU, srcs[d[h]]);
+              uint32_t* dp = &nb[p * PU];
+              for (uint32_t r = 0; r < K; r++) dp[(size_t)r * mi::LANES + lane] = mi::p2_cont_drow(src, live, r);
               for (uint32_t r = 0; r < 3 * (K + 4); r++) {
                 const size_t row = (size_t)(4 * K + 8) + r;
-                nb[p][row * mi::LANES + lane] = mi::p2_cont_drow(src, live, row);
+                dp[row * mi::LANES + lane] = mi::p2_cont_drow(src, live, row);
               }
             }
           run_pairs(nb, next, it, it + 1);
@@ -338,35 +294,16 @@ extern "C" int emu_decode_llr(const mi_dl_sf_cfg_t* cfgs, uint32_t n, const floa
       }
     }
   }
-  for (const MiGroupDesc& g : P.groups) {
-    if (g_x == 3 && g_q16) break;
-    float* sbg = &sb[g.sb_off];
-    uint8_t* map = reinterpret_cast<uint8_t*>(sbg + mi::sb_map_off(g.Ncb));
-    for (uint32_t p = 0; p < g.Ncb; p++) mi::rm_combine_row(&P.lanes[g.lane0], P.kdata.data(), e.data(), sbg, g.Ncb, p,
-                                                              &P.kdata[P.ktabs[g.ktab].ipos_off]);
+  for (size_t gi = 0; gi < P.groups.size() && !p2; gi++) {
+    const MiGroupDesc& g = P.groups[gi];
     const MiKTab& kt = P.ktabs[g.ktab];
-    std::vector<uint32_t> wm(g.K / mi::BETA_W + 1);
-    for (uint32_t w = 0; w < wm.size(); w++) wm[w] = mi::tdec_window_mask(map, &P.kdata[kt.pos_off], w);
-    int16_t* q16 = reinterpret_cast<int16_t*>(&scr[g.scratch_off]) + mi::q16_elem_off(g.K);
     for (int lane = 0; lane < mi::LANES; lane++) {
       const uint32_t li = g.lane0 + lane;
       const MiLaneDesc& ld = P.lanes[li];
       if (!ld.valid) continue;
       mi::TdecArgs a;
-      a.sb = sbg;
-      a.wm = wm.data();
-      a.zrow = g.Ncb;
-      a.q16 = q16;
-      a.pos = &P.kdata[kt.pos_off];
-      a.pi = &P.kdata[kt.pi_off];
-      a.crc_a = &P.kdata[kt.crca_off];
-      a.crc_b = &P.kdata[kt.crcb_off];
-      a.crc8 = crc8;
-      a.scr = &scr[g.scratch_off];
-      a.dec = &dec[g.dec_off];
-      a.cb_bytes = &cbb[(size_t)li * mi::CB_BYTES_STRIDE];
-      a.K = g.K; a.F = ld.F; a.max_its = max_its; a.early_stop = 1; a.crc24a = ld.crc24a;
-      mi::TdecLaneResult r = g_win && g_q16 ? emu_win_cb(g, kt, ld, sbg, P.kdata.data(), lane, max_its, a.cb_bytes)
+      mi::tdec_lane_args(a, m, (uint32_t)gi, g, kt, li, ld, crc8, max_its, 1);
+      mi::TdecLaneResult r = g_win && g_q16 ? emu_win_cb(g, kt, ld, a.sb, m.kdata, lane, max_its, a.cb_bytes)
                            : g_x ? (g_q16 ? emu_lane_x<true>(a, lane) : emu_lane_x<false>(a, lane))
                            : g_q16 ? mi::tdec_lane<true>(a, lane) : mi::tdec_lane<false>(a, lane);
       cits[li] = r.its;
@@ -382,7 +319,7 @@ extern "C" int emu_decode_llr(const mi_dl_sf_cfg_t* cfgs, uint32_t n, const floa
       const uint8_t* src = &cbb[(size_t)lanes[r] * mi::CB_BYTES_STRIDE + (r == 0 ? tb.F / 8 : 0)];
       buf.insert(buf.end(), src, src + mi::tb_cb_nbytes(tb, r));
     }
-    if (!(g_x == 3 && g_q16)) memcpy(payload + tb.pay_off, buf.data(), tb.tbs / 8);   // p2: written in place
+    if (!p2) memcpy(payload + tb.pay_off, buf.data(), tb.tbs / 8);   // p2: written in place
     // TB CRC from the decoder's per-code-block partial registers (tb_kernel's formulation)
     uint32_t crc = 0;
     for (uint32_t r = 0; r < tb.C; r++) crc ^= mi::tb_crc_term(tb, r, ctbp[lanes[r]]);

@@ -287,6 +287,19 @@ int Engine::plan_memo(const mi_dl_sf_cfg_t* cfgs, uint32_t n, bool with_pdsch, h
   return ensure_work(st, false);
 }
 
+Engine::StageMarks Engine::stage_marks(const hipStream_t* cur, bool* ok) {
+  StageMarks m{nullptr, cur, ok};
+  if (!(flags & MI_DL_FLAG_PROFILE)) return m;
+  if (ev_used == ev_sets.size()) {
+    std::vector<hipEvent_t> set(MI_DL_NSTAGES + 1);
+    for (auto& e : set)
+      if (!hip_ok(hipEventCreate(&e), "event")) { *ok = false; return m; }
+    ev_sets.push_back(set);
+  }
+  m.ev = ev_sets[ev_used++].data();
+  return m;
+}
+
 int Engine::run(const void* d_iq, hipStream_t st, uint32_t mask, float* sb_override, const hipStream_t* back) {
   const Plan& P = plan;
   // after a split run, any run of this batch (split or not, on any stream) waits for that run's back end: it rewrites
@@ -298,21 +311,9 @@ int Engine::run(const void* d_iq, hipStream_t st, uint32_t mask, float* sb_overr
   last_stream = back ? *back : st;
   // the stream the next launches go to: st, then (split run) the back-end stream from the hand-off on
   hipStream_t cur = st;
-  const bool prof = flags & MI_DL_FLAG_PROFILE;
-  hipEvent_t* ev = nullptr;
-  if (prof) {
-    if (ev_used == ev_sets.size()) {
-      std::vector<hipEvent_t> set(MI_DL_NSTAGES + 1);
-      for (auto& e : set)
-        if (!hip_ok(hipEventCreate(&e), "event")) return -1;
-      ev_sets.push_back(set);
-    }
-    ev = ev_sets[ev_used++].data();
-  }
   bool ok = true;
-  auto mark = [&](int i) {
-    if (prof) ok = hip_ok(hipEventRecord(ev[i], cur), "event") && ok;
-  };
+  const StageMarks mark = stage_marks(&cur, &ok);
+  if (!ok) return -1;
   // split run: the back-end stream waits for the front end, and the launches from here on go to it
   auto handoff = [&]() {
     if (!back) return;
@@ -397,21 +398,9 @@ int Engine::run(const void* d_iq, hipStream_t st, uint32_t mask, float* sb_overr
 int Engine::run_codeblocks(const float* d_in, hipStream_t st) {
   const Plan& P = plan;
   last_stream = st;
-  const bool prof = flags & MI_DL_FLAG_PROFILE;
-  hipEvent_t* ev = nullptr;
-  if (prof) {
-    if (ev_used == ev_sets.size()) {
-      std::vector<hipEvent_t> set(MI_DL_NSTAGES + 1);
-      for (auto& e : set)
-        if (!hip_ok(hipEventCreate(&e), "event")) return -1;
-      ev_sets.push_back(set);
-    }
-    ev = ev_sets[ev_used++].data();
-  }
   bool ok = true;
-  auto mark = [&](int i) {
-    if (prof) ok = hip_ok(hipEventRecord(ev[i], st), "event") && ok;
-  };
+  const StageMarks mark = stage_marks(&st, &ok);
+  if (!ok) return -1;
   for (int i = 0; i <= MI_DL_STAGE_RM; i++) mark(i);
   launch_cb_scatter(d_in, d_sb.as<float>(), d_groups.as<MiGroupDesc>(), d_ktabs.as<MiKTab>(), d_kdata.as<uint32_t>(),
                     (uint32_t)P.groups.size(), P.cb_K, P.cb_n, st);
@@ -471,29 +460,40 @@ uint32_t Engine::cont_max_pairs() const { return (uint32_t)((plan.lanes.size() +
 bool Engine::launch_turbo(float* sb, hipStream_t st) {
   const Plan& P = plan;
   tb_copied = false;
+  const bool p2 = !use_win() && tdec_crossed() == 3 && q16();
+  // PDSCH batches: the packed decoder writes the payload bytes in place (tb_kernel then only combines the CRCs)
+  const bool direct = p2 && P.has_pdsch && !P.cb_n;
+  TdecBufs b;
+  b.sb = sb;
+  b.wm = d_wm.as<uint32_t>();
+  b.scratch = d_scratch.as<float>();
+  b.dec = d_dec.as<uint8_t>();
+  b.out.cb_bytes = d_cbbytes.as<uint8_t>();
+  b.out.its = d_cbits.as<uint32_t>();
+  b.out.crc_ok = d_cbcrc.as<uint32_t>();
+  b.out.tb_part = d_cbtbp.as<uint32_t>();
+  b.out.payload = direct ? d_payload.as<uint8_t>() : nullptr;
+  b.groups = d_groups.as<MiGroupDesc>();
+  b.lanes = d_lanes.as<MiLaneDesc>();
+  b.ktabs = d_ktabs.as<MiKTab>();
+  b.kdata = d_kdata.as<uint32_t>();
   if (use_win()) {
     uint32_t kmax = 0;
     for (const MiGroupDesc& g : P.groups) kmax = std::max(kmax, g.K);
     // threads per code block: segments of >= ~16 trellis steps (fewer fix-up rounds), at most 256
     uint32_t th = win_threads ? win_threads : opts.win_threads;
     if (!th) th = kmax >= 4096 ? 256 : kmax >= 1024 ? 128 : 64;
-    launch_tdec_win(sb, d_cbbytes.as<uint8_t>(), d_cbits.as<uint32_t>(), d_cbcrc.as<uint32_t>(), d_cbtbp.as<uint32_t>(),
-                    d_groups.as<MiGroupDesc>(), d_lanes.as<MiLaneDesc>(), d_ktabs.as<MiKTab>(), d_kdata.as<uint32_t>(),
-                    (uint32_t)P.lanes.size(), kmax, max_its, early_stop, th, st);
+    launch_tdec_win(b, (uint32_t)P.lanes.size(), kmax, max_its, early_stop, th, st);
     return true;
   }
-  const bool p2 = tdec_crossed() == 3 && q16();
   // compaction needs its buffers (ensure_work sized them for this plan and max_its); without them the
   // packed decoder runs every iteration itself -- the same results either way
   const bool cont = p2 && tdec_compact() && d_cscr.bytes >= (size_t)cont_max_pairs() * cont_pair_u32() * 4 &&
                     d_cont.bytes >= (3 * P.lanes.size() + 2) * 4 &&
                     d_cdec.bytes >= (size_t)cont_max_pairs() * P.groups[0].K * LANES;
   // (the row masks' kernel also resets the continuation's count: no memset launch between the decoder and its assign)
-  launch_rowmask(sb, d_wm.as<uint32_t>(), d_groups.as<MiGroupDesc>(), d_ktabs.as<MiKTab>(), d_kdata.as<uint32_t>(),
-                 (uint32_t)P.groups.size(), cont ? d_cont.as<uint32_t>() : nullptr, st);
+  launch_rowmask(b, (uint32_t)P.groups.size(), cont ? d_cont.as<uint32_t>() : nullptr, st);
   if (p2) {
-    // PDSCH batches: the decoder writes the payload bytes in place (tb_kernel then only combines the CRCs)
-    const bool direct = P.has_pdsch && !P.cb_n;
     tb_copied = direct;
     // The one-iteration first launch stores no extrinsic rows w when few code blocks continue (the continuation
     // re-forms them by re-running iteration 0's DEC2 from gathered x2 rows: 12 KB per code block less for all, about
@@ -518,30 +518,34 @@ bool Engine::launch_turbo(float* sb, hipStream_t st) {
                 : cont_mode >= 0     ? cont_mode != 0
                                      : (uint64_t)cont_last[0] * 50 > P.lanes.size();
     }
-    launch_tdec_p2(sb, d_wm.as<uint32_t>(), d_scratch.as<float>(), d_dec.as<uint8_t>(), d_cbbytes.as<uint8_t>(),
-                   d_cbits.as<uint32_t>(), d_cbcrc.as<uint32_t>(), d_cbtbp.as<uint32_t>(), d_groups.as<MiGroupDesc>(),
-                   d_lanes.as<MiLaneDesc>(), d_ktabs.as<MiKTab>(), d_kdata.as<uint32_t>(), d_pairs.as<uint32_t>(),
-                   (uint32_t)(P.pairs.size() / 2), cont ? 1u : max_its, early_stop, direct ? d_payload.as<uint8_t>() : nullptr,
+    launch_tdec_p2(b, d_pairs.as<uint32_t>(), (uint32_t)(P.pairs.size() / 2), cont ? 1u : max_its, early_stop,
                    cont && !store_w, st);
     if (cont) {
       // the code blocks still failing after iteration 0, compacted into dense pairs for iterations 1 ..
+      const uint32_t K = P.groups[0].K;
+      const size_t ssz = (size_t)LANES * (2 * K + 8 * (K / TDEC_CK_MIN + 1));   // a group's scratch (plan.cpp)
+      TdecContBufs c;
+      c.cont = d_cont.as<uint32_t>();
+      c.cscr = d_cscr.as<uint32_t>();
+      c.cdec = d_cdec.as<uint8_t>();
+      c.max_pairs = cont_max_pairs();
+      c.pair_u32 = cont_pair_u32();
+      c.scr_pair_u32 = 2 * ssz;
+      TdecContSched s;
+      // the gather is grid-stride: when the history continued nothing, a small grid (its 2048 early-exiting
+      // workgroups otherwise wait ~1 ms for CU slots behind the other streams' decoders)
+      s.gather_wgs = (cont_mode >= 0 ? cont_mode != 0 : cont_last[0] || cont_last[1]) ? 2048u : 64u;
+      s.w_stored = store_w;
       // many continuing code blocks (the same history): one iteration per launch, re-compacting the code blocks that
       // still fail between them, so a pair no longer runs until its slowest of 128 code blocks stops (21.5 dB:
       // 379 + 84 + 19 pair-iterations instead of 3 x 379).  Opts::rounds forces (A/B).
-      const bool rounds = opts.rounds >= 0 ? opts.rounds != 0 : store_w;
-      const size_t ssz = (size_t)LANES * (2 * P.groups[0].K + 8 * (P.groups[0].K / TDEC_CK_MIN + 1));   // plan.cpp
-      if (!launch_tdec_cont(sb, d_wm.as<uint32_t>(), d_scratch.as<float>(), 2 * ssz, d_dec.as<uint8_t>(),
-                       d_cbbytes.as<uint8_t>(), d_cbits.as<uint32_t>(),
-                       d_cbcrc.as<uint32_t>(), d_cbtbp.as<uint32_t>(), d_groups.as<MiGroupDesc>(),
-                       d_lanes.as<MiLaneDesc>(), d_kdata.as<uint32_t>(), P.ktabs[P.groups[0].ktab],
-                       (uint32_t)P.groups.size(), d_cont.as<uint32_t>(), d_cscr.as<uint32_t>(), d_cdec.as<uint8_t>(),
-                       cont_max_pairs(), cont_pair_u32(), P.groups[0].K, max_its,
-                       // the gather is grid-stride: when the history continued nothing, a small grid (its 2048
-                       // early-exiting workgroups otherwise wait ~1 ms for CU slots behind the other streams' decoders)
-                       (cont_mode >= 0 ? cont_mode != 0 : cont_last[0] || cont_last[1]) ? 2048u : 64u,
-                       direct ? d_payload.as<uint8_t>() : nullptr, store_w, rounds, cont_pending ? nullptr : h_cont,
-                       opts.seg == 4 || opts.seg == 8 ? (uint32_t)opts.seg
-                       : opts.seg < 0 && (flags & MI_DL_FLAG_TDEC_SEG) ? 8u : 0u, true, st))
+      s.rounds = opts.rounds >= 0 ? opts.rounds != 0 : store_w;
+      s.seg = opts.seg == 4 || opts.seg == 8                    ? (uint32_t)opts.seg
+              : opts.seg < 0 && (flags & MI_DL_FLAG_TDEC_SEG) ? 8u
+                                                               : 0u;
+      s.h_count = cont_pending ? nullptr : h_cont;
+      s.cont_zeroed = true;   // by launch_rowmask above
+      if (!launch_tdec_cont(b, c, s, (uint32_t)P.groups.size(), P.ktabs[P.groups[0].ktab], K, max_its, st))
         return false;
       // the copy of the count (skipped while an earlier one is still unread) is complete when cont_ev is
       if (!cont_pending) {
@@ -551,10 +555,7 @@ bool Engine::launch_turbo(float* sb, hipStream_t st) {
     }
     return true;
   }
-  launch_tdec(sb, d_wm.as<uint32_t>(), d_scratch.as<float>(), d_dec.as<uint8_t>(), d_cbbytes.as<uint8_t>(),
-              d_cbits.as<uint32_t>(), d_cbcrc.as<uint32_t>(), d_cbtbp.as<uint32_t>(), d_groups.as<MiGroupDesc>(),
-              d_lanes.as<MiLaneDesc>(), d_ktabs.as<MiKTab>(), d_kdata.as<uint32_t>(), (uint32_t)P.groups.size(),
-              max_its, early_stop, q16(), tdec_crossed(), st);
+  launch_tdec(b, (uint32_t)P.groups.size(), max_its, early_stop, q16(), tdec_crossed(), st);
   return true;
 }
 

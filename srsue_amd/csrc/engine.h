@@ -59,6 +59,7 @@ struct Engine {
   bool tdec_compact() const;
   size_t cont_pair_u32() const;   // continuation pair scratch, u32 words
   uint32_t cont_max_pairs() const;
+  // the turbo stage: builds the buffer view (kernels.h TdecBufs) once and hands it to every launcher
   bool launch_turbo(float* sb, hipStream_t st);   // false: a HIP call failed (mi_last_error)
   bool tb_copied = false;
   // the last turbo stage wrote the payload bytes itself (packed decoder, PDSCH batch)
@@ -124,6 +125,18 @@ struct Engine {
   // profiling: one event set per run since the last reset (MI_DL_FLAG_PROFILE)
   std::vector<std::vector<hipEvent_t>> ev_sets;
   size_t ev_used = 0;
+  // a run's stage marks: mark(i) records event i of the run's set on *cur (the stream the run's launches go to at
+  // that point) and clears *ok on a HIP error; nothing when the run is not profiled
+  struct StageMarks {
+    hipEvent_t* ev;
+    const hipStream_t* cur;
+    bool* ok;
+    void operator()(int i) const {
+      if (ev) *ok = hip_ok(hipEventRecord(ev[i], *cur), "event") && *ok;
+    }
+  };
+  // the marks of a run that starts now, with a fresh event set when profiling (*ok cleared if it cannot be created)
+  StageMarks stage_marks(const hipStream_t* cur, bool* ok);
   int device = 0;
 
   ~Engine();

@@ -1,4 +1,6 @@
 // kernels.h -- host launchers of the gfx950 kernels of the DL PDSCH path.
+// The turbo launchers take the stage's buffers as typed views (TdecBufs, TdecContBufs, TdecContSched) and unpack them
+// into their kernels' individual __restrict__ pointer parameters.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dl_common.h"
@@ -34,46 +36,68 @@ void launch_rm_fused(const float2* grid, const float2* ce, const MiLaneSrc* lane
                      bool compact_ce, hipStream_t st);
 // row maps and zero rows of Plan::rm_direct's groups (rm.hip rm_direct_map_kernel), before the combine launch
 void launch_rm_direct_maps(float* sb, const uint32_t* ktab_data, const MiRmDirect* dgs, uint32_t ndg, hipStream_t st);
-// turbo decoder (srslte_tdec_*): one wavefront per group of 64 code blocks
-// window masks of the sparse softbuffer rows (which decoder inputs have a materialised row)
-void launch_rowmask(const float* sb, uint32_t* wm, const MiGroupDesc* groups, const MiKTab* ktabs,
-                    const uint32_t* kdata, uint32_t n_groups, uint32_t* zero, hipStream_t st);
-void launch_tdec(const float* sb, const uint32_t* wm, float* scratch, uint8_t* dec, uint8_t* cb_bytes, uint32_t* cb_its,
-                 uint32_t* cb_crc, uint32_t* cb_tbp, const MiGroupDesc* groups, const MiLaneDesc* lanes,
-                 const MiKTab* ktabs, const uint32_t* ktab_data, uint32_t n_groups, uint32_t max_its,
-                 uint32_t early_stop, bool q16, int crossed /* 0 one wavefront per group, 1 crossed, 2 crossed recompute */, hipStream_t st);
+// ---- turbo decoder (srslte_tdec_*) ----
+// per code block (lane index li) results
+struct TdecOut {
+  uint8_t* cb_bytes;        // [li][CB_BYTES_STRIDE] packed decisions
+  uint32_t* its;            // iterations used
+  uint32_t* crc_ok;         // CB CRC verdict of the last iteration
+  uint32_t* tb_part;        // partial TB-CRC24A register (tb_kernel combines them)
+  uint8_t* payload;         // packed decoder, PDSCH batches: payload bytes written in place (MiLaneDesc pay_st /
+                            // pay_n), no code-block rows; nullptr = rows
+};
+// The turbo stage's buffers, built once per run (Engine::launch_turbo) and taken by every turbo launcher, which unpacks
+// it into its kernels' individual __restrict__ pointer parameters
+struct TdecBufs {
+  const float* sb;          // softbuffer arena
+  uint32_t* wm;             // window masks, WM_STRIDE per group (launch_rowmask writes them, the decoders read them)
+  float* scratch;
+  uint8_t* dec;
+  TdecOut out;
+  const MiGroupDesc* groups;
+  const MiLaneDesc* lanes;
+  const MiKTab* ktabs;
+  const uint32_t* kdata;
+};
+// the waterfall continuation's buffers and their sizes
+struct TdecContBufs {
+  uint32_t* cont;           // the lists: 1 + lanes words; with rounds 3 n_groups * 64 + 2 (two lists and the sources)
+  uint32_t* cscr;           // max_pairs x pair_u32 words: the dense pairs' state
+  uint8_t* cdec;            // max_pairs x K x 64 decision bytes
+  uint32_t max_pairs;
+  size_t pair_u32;
+  size_t scr_pair_u32;      // rounds: the stride of a group pair's own scratch, reused (with dec) as pair buffers
+};
+// and its schedule
+struct TdecContSched {
+  uint32_t gather_wgs;      // workgroups of the (grid-stride) gathers
+  bool w_stored;            // the first launch stored w rows: gather them (no DEC2 re-run)
+  bool rounds;              // one iteration per launch, the failing code blocks re-compacted between them
+  uint32_t seg;             // rounds: 0, or the rounds after the first segmented over 4 / 8 wavefronts per pair
+                            // (tdec_kernel_p2s)
+  uint32_t* h_count;        // page-locked [CONT_HIST]: the code blocks each round decodes (round 1: those continuing
+                            // after iteration 0); nullptr = not recorded
+  bool cont_zeroed;         // cont[0] already reset on the stream (launch_rowmask's zero)
+};
+constexpr uint32_t CONT_HIST = 8;   // rounds whose counts are recorded (h_count)
+// window masks of the sparse softbuffer rows (which decoder inputs have a materialised row); zero (if set) is reset
+void launch_rowmask(const TdecBufs& b, uint32_t n_groups, uint32_t* zero, hipStream_t st);
+// one wavefront per group of 64 code blocks
+void launch_tdec(const TdecBufs& b, uint32_t n_groups, uint32_t max_its, uint32_t early_stop, bool q16,
+                 int crossed /* 0 one wavefront per group, 1 crossed, 2 crossed recompute */, hipStream_t st);
 // packed int16 decoder, two code blocks per lane: one workgroup (crossed wavefronts F and B) per group pair
 // (Plan::pairs)
-void launch_tdec_p2(const float* sb, const uint32_t* wm, float* scratch, uint8_t* dec, uint8_t* cb_bytes,
-                    uint32_t* cb_its, uint32_t* cb_crc, uint32_t* cb_tbp, const MiGroupDesc* groups,
-                    const MiLaneDesc* lanes, const MiKTab* ktabs, const uint32_t* ktab_data, const uint32_t* pairs,
-                    uint32_t n_pairs, uint32_t max_its, uint32_t early_stop,
-                    uint8_t* payload /* PDSCH batches: payload bytes written in place; nullptr = cb_bytes rows */,
+void launch_tdec_p2(const TdecBufs& b, const uint32_t* pairs, uint32_t n_pairs, uint32_t max_its, uint32_t early_stop,
                     bool no_w /* DEC2 stores no extrinsic rows (a one-iteration first launch, tdec_p2_body.h) */,
                     hipStream_t st);
 // waterfall compaction after iteration 0 of launch_tdec_p2 (one K, early stop; tdec_p2_body.h P2ContSrc):
-// gather the CRC-failing code blocks into dense continuation pairs (cscr: max_pairs x pair_u32 words, cdec:
-// max_pairs x K x 64 bytes, cont: 1 + lanes words) and decode iterations 1 .. max_its - 1 there
-bool launch_tdec_cont(const float* sb, const uint32_t* wm, float* scratch, size_t scr_pair_u32, uint8_t* dec,
-                      uint8_t* cb_bytes, uint32_t* cb_its, uint32_t* cb_crc, uint32_t* cb_tbp, const MiGroupDesc* groups,
-                      const MiLaneDesc* lanes, const uint32_t* ktab_data, const MiKTab& kt, uint32_t n_groups, uint32_t* cont,
-                      uint32_t* cscr, uint8_t* cdec, uint32_t max_pairs, size_t pair_u32, uint32_t K, uint32_t max_its,
-                      uint32_t gather_wgs, uint8_t* payload,
-                      bool w_stored /* the first launch stored w rows: gather them (no DEC2 re-run) */,
-                      bool rounds /* one iteration per launch, the failing code blocks re-compacted between them;
-                                     cont holds 3 n_groups * 64 + 2 words, scratch / dec are reused as pair buffers */,
-                      uint32_t* h_count /* page-locked [CONT_HIST]: the code blocks each round decodes (round 1:
-                                           those continuing after iteration 0) */,
-                      uint32_t seg /* 0, or the rounds after the first segmented over 4 / 8 wavefronts per pair
-                                      (tdec_kernel_p2s) */,
-                      bool cont_zeroed /* cont[0] already reset on st (launch_rowmask's zero) */, hipStream_t st);
-constexpr uint32_t CONT_HIST = 8;   // rounds whose counts are recorded (h_count)
+// gather the CRC-failing code blocks into dense continuation pairs and decode iterations 1 .. max_its - 1 there
+bool launch_tdec_cont(const TdecBufs& b, const TdecContBufs& c, const TdecContSched& s, uint32_t n_groups,
+                      const MiKTab& kt, uint32_t K, uint32_t max_its, hipStream_t st);
 // latency form of the int16 turbo decoder: one workgroup of `threads` (64/128/256) per code block
 // (lane descriptor), exact trellis segments (tdec_win_body.h); max_k sizes the dynamic LDS
-void launch_tdec_win(const float* sb, uint8_t* cb_bytes, uint32_t* cb_its, uint32_t* cb_crc, uint32_t* cb_tbp,
-                     const MiGroupDesc* groups, const MiLaneDesc* lanes, const MiKTab* ktabs, const uint32_t* kdata,
-                     uint32_t n_lanes, uint32_t max_k, uint32_t max_its, uint32_t early_stop, uint32_t threads,
-                     hipStream_t st);
+void launch_tdec_win(const TdecBufs& b, uint32_t n_lanes, uint32_t max_k, uint32_t max_its, uint32_t early_stop,
+                     uint32_t threads, hipStream_t st);
 // raw code-block decoder input [cb][3(K+4)] -> group-interleaved softbuffer layout
 void launch_cb_scatter(const float* d, float* sb, const MiGroupDesc* groups, const MiKTab* ktabs,
                        const uint32_t* kdata, uint32_t n_groups, uint32_t K, uint32_t n_cb, hipStream_t st);

@@ -36,6 +36,18 @@ MI_HD inline uint32_t crc24_byte_entry(uint32_t b, uint32_t poly) {
   for (int i = 0; i < 8; i++) c = ((c << 1) & 0xFFFFFFu) ^ ((c & 0x800000u) ? poly : 0u);
   return c;
 }
+// entries t0, t0 + step, ... of the CRC24A byte table, and of the CRC24B one beside it: a workgroup's threads fill its
+// LDS tables between them (t0 = the thread; the caller's barrier follows), the host fills them with (0, 1)
+MI_HD __attribute__((always_inline)) inline void crc24_fill_tables(uint32_t* crc8, uint32_t t0, uint32_t step) {
+  for (uint32_t b = t0; b < 256; b += step) crc8[b] = crc24_byte_entry(b, CRC24A_POLY);
+}
+MI_HD __attribute__((always_inline)) inline void crc24_fill_tables(uint32_t* crc8, uint32_t* crc8b, uint32_t t0,
+                                                                   uint32_t step) {
+  for (uint32_t b = t0; b < 256; b += step) {
+    crc8[b] = crc24_byte_entry(b, CRC24A_POLY);
+    crc8b[b] = crc24_byte_entry(b, CRC24B_POLY);
+  }
+}
 
 // a * b mod (x^24 + poly) over GF(2)
 MI_HD inline uint32_t gf24_mulmod(uint32_t a, uint32_t b, uint32_t poly) {

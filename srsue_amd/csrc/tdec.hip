@@ -7,22 +7,6 @@
 
 namespace mi {
 
-struct TdecOut {            // per code block (lane index li) results
-  uint8_t* cb_bytes;        // [li][CB_BYTES_STRIDE] packed decisions
-  uint32_t* its;            // iterations used
-  uint32_t* crc_ok;         // CB CRC verdict of the last iteration
-  uint32_t* tb_part;        // partial TB-CRC24A register (tb_kernel combines them)
-  uint8_t* payload;         // packed decoder, PDSCH batches: payload bytes written in place (MiLaneDesc pay_st /
-                            // pay_n), no code-block rows; nullptr = rows
-};
-// the packed decoder's output of one half: the code block's payload run, or its row; crc24a bit 1 = the code
-// block carries the TB CRC (tdec_p2_check)
-__device__ inline void p2_out(TdecArgsP2& a, int h, const TdecOut& out, uint32_t li, const MiLaneDesc& ld) {
-  a.out_bytes = out.payload ? out.payload : out.cb_bytes;
-  a.cb_off[h] = out.payload ? ld.pay_st : li * CB_BYTES_STRIDE;
-  a.crc24a[h] = ld.crc24a | (ld.tbcrc << 1);
-}
-
 // crossed schedule (tdec_body.h tdec_lane_x): wave 0 = F, wave 1 = B of the same 64 code blocks
 struct TdecExecGpu {
   static constexpr bool SHARED = true;
@@ -50,7 +34,7 @@ __device__ __forceinline__ void tdec_group(const float* __restrict__ sb, const u
   // CRC24A byte table in LDS (one entry per lane group of 4), for the TB-CRC partial of each lane
   __shared__ uint32_t crc8[256];
   __shared__ uint32_t xcrc[X ? 2 * LANES : 1];
-  for (uint32_t b = threadIdx.x; b < 256; b += blockDim.x) crc8[b] = crc24_byte_entry(b, CRC24A_POLY);
+  crc24_fill_tables(crc8, threadIdx.x, blockDim.x);
   __syncthreads();
   const MiGroupDesc g = groups[blockIdx.x];
   const MiKTab kt = ktabs[g.ktab];
@@ -58,24 +42,9 @@ __device__ __forceinline__ void tdec_group(const float* __restrict__ sb, const u
   const uint32_t li = g.lane0 + lane;
   const MiLaneDesc ld = lanes[li];
   if (!ld.valid) return;
+  const TdecMem m{sb, wm, scratch, dec, out.cb_bytes, nullptr, kdata};
   TdecArgs a;
-  a.sb = sb + g.sb_off;
-  a.wm = wm + (size_t)blockIdx.x * WM_STRIDE;
-  a.zrow = g.Ncb;
-  a.q16 = reinterpret_cast<int16_t*>(scratch + g.scratch_off) + q16_elem_off(g.K);
-  a.pos = kdata + kt.pos_off;
-  a.pi = kdata + kt.pi_off;
-  a.crc_a = kdata + kt.crca_off;
-  a.crc_b = kdata + kt.crcb_off;
-  a.crc8 = crc8;
-  a.scr = scratch + g.scratch_off;
-  a.dec = dec + g.dec_off;
-  a.cb_bytes = out.cb_bytes + (size_t)li * CB_BYTES_STRIDE;
-  a.K = g.K;
-  a.F = ld.F;
-  a.max_its = max_its;
-  a.early_stop = early_stop;
-  a.crc24a = ld.crc24a;
+  tdec_lane_args(a, m, blockIdx.x, g, kt, li, ld, crc8, max_its, early_stop);
   if constexpr (X) {
     TdecExecGpu ex{(int)(threadIdx.x / LANES), xcrc};
     TdecLaneResult r = tdec_lane_x<Q16, RC>(a, lane, ex);
@@ -107,11 +76,10 @@ __global__ __launch_bounds__(256) void rowmask_kernel(const float* __restrict__ 
   wm[(size_t)blockIdx.y * WM_STRIDE + w] = tdec_window_mask(map, kdata + ktabs[g.ktab].pos_off, w);
 }
 
-void launch_rowmask(const float* sb, uint32_t* wm, const MiGroupDesc* groups, const MiKTab* ktabs,
-                    const uint32_t* kdata, uint32_t n_groups, uint32_t* zero, hipStream_t st) {
+void launch_rowmask(const TdecBufs& b, uint32_t n_groups, uint32_t* zero, hipStream_t st) {
   if (!n_groups) return;
-  hipLaunchKernelGGL(rowmask_kernel, dim3((WM_STRIDE + 255) / 256, n_groups), dim3(256), 0, st, sb, wm, groups,
-                     ktabs, kdata, zero);
+  hipLaunchKernelGGL(rowmask_kernel, dim3((WM_STRIDE + 255) / 256, n_groups), dim3(256), 0, st, b.sb, b.wm, b.groups,
+                     b.ktabs, b.kdata, zero);
 }
 
 // float decoder
@@ -196,19 +164,17 @@ void tdec_kernel_p2x(const float* __restrict__ sb, const uint32_t* __restrict__ 
   __shared__ uint32_t crc8[256], crc8b[256];
   __shared__ uint32_t xs[LANES];
   __shared__ uint32_t stash[2][(ONE ? P2_STASH_ROWS_FIRST : P2_STASH_ROWS) * LANES];
-  for (uint32_t b = threadIdx.x; b < 256; b += blockDim.x) {
-    crc8[b] = crc24_byte_entry(b, CRC24A_POLY);
-    crc8b[b] = crc24_byte_entry(b, CRC24B_POLY);
-  }
+  crc24_fill_tables(crc8, crc8b, threadIdx.x, blockDim.x);
   __syncthreads();
   const uint32_t ga = pairs[2 * blockIdx.x], gbi = pairs[2 * blockIdx.x + 1];
-  const bool paired = gbi != 0xFFFFFFFFu;
-  const uint32_t gb = paired ? gbi : ga;
-  const MiGroupDesc gA = groups[ga], gB = groups[gb];
+  const MiGroupDesc gA = groups[ga], gB = groups[gbi != 0xFFFFFFFFu ? gbi : ga];
   const MiKTab kt = ktabs[gA.ktab];
   const int lane = threadIdx.x % LANES;
   const uint32_t li[2] = {gA.lane0 + lane, gB.lane0 + lane};
   const MiLaneDesc l0 = lanes[li[0]], l1 = lanes[li[1]];
+  // (p2_first_live / p2_first_args of tdec_p2_body.h, spelt out: see there)
+  const bool paired = gbi != 0xFFFFFFFFu;
+  const uint32_t gb = paired ? gbi : ga;
   TdecArgsP2 a;
   a.live = (l0.valid ? 1u : 0u) | (paired && l1.valid ? 2u : 0u);
   if (!a.live) return;   // the same on both wavefronts: no barrier is left waiting
@@ -226,9 +192,9 @@ void tdec_kernel_p2x(const float* __restrict__ sb, const uint32_t* __restrict__ 
   a.crc8 = crc8;
   a.crc8b = crc8b;
   a.dec = dec + gA.dec_off;
-  p2_out(a, 0, out, li[0], l0);
-  if (a.live & 2u) p2_out(a, 1, out, li[1], l1);
-  else p2_out(a, 1, out, li[0], l0);
+  p2_out(a, 0, out.cb_bytes, out.payload, li[0], l0);
+  if (a.live & 2u) p2_out(a, 1, out.cb_bytes, out.payload, li[1], l1);
+  else p2_out(a, 1, out.cb_bytes, out.payload, li[0], l0);
   a.to_payload = out.payload != nullptr;
   a.K = K;
   a.F[0] = l0.F;
@@ -242,7 +208,7 @@ void tdec_kernel_p2x(const float* __restrict__ sb, const uint32_t* __restrict__ 
   const TdecP2Result r = tdec_p2_lane<false, P2_CKS, ONE, FIXED ? 0u : TDEC_MKQ_IT>(a, lane, ex);
   if (ex.wave) return;
 #pragma unroll
-  for (int h = 0; h < 2; h++) {
+  for (int h = 0; h < 2; h++) {   // (p2_put_result, likewise)
     if (!((a.live >> h) & 1u)) continue;
     out.its[li[h]] = r.its[h];
     out.crc_ok[li[h]] = r.crc_ok[h];
@@ -250,23 +216,17 @@ void tdec_kernel_p2x(const float* __restrict__ sb, const uint32_t* __restrict__ 
   }
 }
 
-void launch_tdec_p2(const float* sb, const uint32_t* wm, float* scratch, uint8_t* dec, uint8_t* cb_bytes,
-                    uint32_t* cb_its, uint32_t* cb_crc, uint32_t* cb_tbp, const MiGroupDesc* groups,
-                    const MiLaneDesc* lanes, const MiKTab* ktabs, const uint32_t* ktab_data, const uint32_t* pairs,
-                    uint32_t n_pairs, uint32_t max_its, uint32_t early_stop, uint8_t* payload, bool no_w,
-                    hipStream_t st) {
+void launch_tdec_p2(const TdecBufs& b, const uint32_t* pairs, uint32_t n_pairs, uint32_t max_its, uint32_t early_stop,
+                    bool no_w, hipStream_t st) {
   if (!n_pairs) return;
-  const TdecOut out{cb_bytes, cb_its, cb_crc, cb_tbp, payload};
+  auto go = [&](auto kernel, uint32_t nw) {
+    hipLaunchKernelGGL(kernel, dim3(n_pairs), dim3(128), 0, st, b.sb, b.wm, b.scratch, b.dec, b.out, b.groups, b.lanes,
+                       b.ktabs, b.kdata, pairs, max_its, early_stop, nw);
+  };
   // a one-iteration launch (the compacted path's first, beside other streams' rate de-matching): the smaller stash
-  if (max_its > 1 && !early_stop)
-    hipLaunchKernelGGL((tdec_kernel_p2x<false, true>), dim3(n_pairs), dim3(128), 0, st, sb, wm, scratch, dec, out,
-                       groups, lanes, ktabs, ktab_data, pairs, max_its, early_stop, 0u);
-  else if (max_its > 1)
-    hipLaunchKernelGGL(tdec_kernel_p2x<false>, dim3(n_pairs), dim3(128), 0, st, sb, wm, scratch, dec, out, groups,
-                       lanes, ktabs, ktab_data, pairs, max_its, early_stop, 0u);
-  else
-    hipLaunchKernelGGL(tdec_kernel_p2x<true>, dim3(n_pairs), dim3(128), 0, st, sb, wm, scratch, dec, out, groups,
-                       lanes, ktabs, ktab_data, pairs, max_its, early_stop, (uint32_t)no_w);
+  if (max_its > 1 && !early_stop) go(tdec_kernel_p2x<false, true>, 0u);
+  else if (max_its > 1) go(tdec_kernel_p2x<false>, 0u);
+  else go(tdec_kernel_p2x<true>, (uint32_t)no_w);
 }
 
 // ---- waterfall compaction (tdec_p2_body.h P2ContSrc): one K, early stop, iteration 0 done by
@@ -276,20 +236,26 @@ void launch_tdec_p2(const float* sb, const uint32_t* wm, float* scratch, uint8_t
 // clamps a count it reads from memory to it and writes no slot beyond it, so two runs of one workspace racing on two
 // unordered streams (a caller error: a batch runs on one stream at a time) cannot take a kernel out of its buffers
 __device__ __forceinline__ uint32_t cont_count(const uint32_t* list, uint32_t cap) { return min(list[0], cap); }
+// the lanes of a wavefront with act set claim consecutive slots of the list whose count is *counter: one atomic per
+// wavefront (the first claiming lane's), each lane's slot from the ballot's prefix.  The slot is meaningful where act
+__device__ __forceinline__ uint32_t cont_claim(bool act, uint32_t* counter) {
+  const uint32_t lane = threadIdx.x;   // one wavefront per workgroup
+  const uint64_t m = __ballot(act);
+  if (!m) return 0u;
+  const int lead = __ffsll((unsigned long long)m) - 1;
+  uint32_t base = 0;
+  if ((int)lane == lead) base = atomicAdd(counter, (uint32_t)__popcll(m));
+  base = __shfl(base, lead);
+  return base + __popcll(m & ((1ull << lane) - 1ull));
+}
 // 1. one wavefront per group: the lanes whose code block failed its CRC claim consecutive slots
 __global__ __launch_bounds__(64) void tdec_cont_assign_kernel(const MiGroupDesc* __restrict__ groups,
                                                               const MiLaneDesc* __restrict__ lanes,
                                                               const uint32_t* __restrict__ cb_crc, uint32_t* cont,
                                                               uint32_t cap) {
-  const uint32_t lane = threadIdx.x, li = groups[blockIdx.x].lane0 + lane;
+  const uint32_t li = groups[blockIdx.x].lane0 + threadIdx.x;
   const bool act = lanes[li].valid && !cb_crc[li];
-  const uint64_t m = __ballot(act);
-  if (!m) return;
-  const int lead = __ffsll((unsigned long long)m) - 1;
-  uint32_t base = 0;
-  if ((int)lane == lead) base = atomicAdd(cont, (uint32_t)__popcll(m));
-  base = __shfl(base, lead);
-  const uint32_t slot = base + __popcll(m & ((1ull << lane) - 1ull));
+  const uint32_t slot = cont_claim(act, cont);
   if (act && slot < cap) cont[1 + slot] = li;
 }
 
@@ -299,17 +265,11 @@ __global__ __launch_bounds__(64) void tdec_cont_assign_kernel(const MiGroupDesc*
 __global__ __launch_bounds__(64) void tdec_cont_assign2_kernel(const uint32_t* __restrict__ prev,
                                                                const uint32_t* __restrict__ cb_crc, uint32_t* next,
                                                                uint32_t* __restrict__ src, uint32_t cap) {
-  const uint32_t lane = threadIdx.x, d = blockIdx.x * LANES + lane, n = cont_count(prev, cap);
+  const uint32_t d = blockIdx.x * LANES + threadIdx.x, n = cont_count(prev, cap);
   if (blockIdx.x * LANES >= n) return;   // the whole wavefront
   const uint32_t li = d < n ? prev[1 + d] : 0u;
   const bool act = d < n && !cb_crc[li];
-  const uint64_t m = __ballot(act);
-  if (!m) return;
-  const int lead = __ffsll((unsigned long long)m) - 1;
-  uint32_t base = 0;
-  if ((int)lane == lead) base = atomicAdd(next, (uint32_t)__popcll(m));
-  base = __shfl(base, lead);
-  const uint32_t slot = base + __popcll(m & ((1ull << lane) - 1ull));
+  const uint32_t slot = cont_claim(act, next);
   if (act && slot < cap) {
     next[1 + slot] = li;
     src[slot] = d;
@@ -338,13 +298,9 @@ __global__ __launch_bounds__(256) void tdec_cont_gather_kernel(const float* __re
     for (int h = 0; h < 2; h++) {
       const uint32_t d = p * 2 * LANES + h * LANES + lane;
       if (d >= n) continue;
-      const uint32_t li = cont[1 + d], g = li / LANES;   // plan.cpp: group g = lanes 64 g .. 64 g + 63
+      const uint32_t li = cont[1 + d], g = li / LANES;
       live |= 1u << h;
-      s[h].sb = sb + groups[g].sb_off;
-      s[h].wm = wm + (size_t)g * WM_STRIDE;
-      s[h].scr = reinterpret_cast<const uint32_t*>(scratch + groups[g & ~1u].scratch_off);   // pairs (2j, 2j + 1)
-      s[h].ls = li % LANES;
-      s[h].hs = g & 1u;
+      s[h] = p2_cont_src(sb, wm, scratch, groups, li, g & ~1u, g & 1u);   // the first launch's pairs: (2j, 2j + 1)
     }
     uint32_t* dst = cscr + (size_t)p * pair_u32;
     if (c < nqt) {
@@ -385,11 +341,8 @@ __global__ __launch_bounds__(256) void tdec_cont_gather2_kernel(const uint32_t* 
     for (int h = 0; h < 2; h++) {
       const uint32_t d = p * 2 * LANES + h * LANES + lane;
       if (d >= n) continue;
-      const uint32_t e = src[d];   // the previous round's slot: pair e / 128, half (e / 64) % 2, lane e % 64
       live |= 1u << h;
-      s[h].scr = prev + (size_t)(e / (2 * LANES)) * prev_u32;
-      s[h].ls = e % LANES;
-      s[h].hs = (e / LANES) & 1u;
+      s[h] = p2_cont_src2(prev, prev_u32, src[d]);
     }
     uint32_t* dp = dst + (size_t)p * dst_u32;
     // rows [r0, r1): the w rows (at 0) or the q rows (at 4K + 8)
@@ -414,46 +367,19 @@ void tdec_kernel_p2c(uint32_t* __restrict__ cscr, uint8_t* __restrict__ cdec, Td
   __shared__ uint32_t xs[LANES];
   const uint32_t n = cont_count(cont, cap), p = blockIdx.x;
   if ((size_t)p * 2 * LANES >= n) return;   // the whole workgroup
-  for (uint32_t b = threadIdx.x; b < 256; b += blockDim.x) {
-    crc8[b] = crc24_byte_entry(b, CRC24A_POLY);
-    crc8b[b] = crc24_byte_entry(b, CRC24B_POLY);
-  }
+  crc24_fill_tables(crc8, crc8b, threadIdx.x, blockDim.x);
   __syncthreads();
   const int lane = threadIdx.x % LANES;
-  const uint32_t d0 = p * 2 * LANES + lane, d1 = d0 + LANES;
   TdecArgsP2 a{};
-  a.live = (d0 < n ? 1u : 0u) | (d1 < n ? 2u : 0u);
+  uint32_t li[2];
+  a.live = p2_cont_lanes<false>(li, cont, n, p, lane);
   if (!a.live) return;   // the same on both wavefronts
-  const uint32_t li[2] = {cont[1 + d0], (a.live & 2u) ? cont[1 + d1] : cont[1 + d0]};
-  const MiLaneDesc l0 = lanes[li[0]], l1 = lanes[li[1]];
-  a.scr = cscr + (size_t)p * pair_u32;
-  a.q = a.scr + (size_t)(4 * K + 8) * LANES;
-  a.pos = kdata + kt.pos_off;
-  a.pi = kdata + kt.pi_off;
-  a.crc8 = crc8;
-  a.crc8b = crc8b;
-  a.dec = cdec + (size_t)p * dec_stride;
-  p2_out(a, 0, out, li[0], l0);
-  p2_out(a, 1, out, li[1], l1);
-  a.to_payload = out.payload != nullptr;
-  a.K = K;
-  a.F[0] = l0.F;
-  a.F[1] = l1.F;
-  a.max_its = max_its;
-  a.early_stop = 1;
-  a.cont_w = w_stored;
-  a.it0 = it0;
-  a.it_end = it_end;
+  p2_cont_args(a, li, p, cscr, pair_u32, cdec, dec_stride, out.cb_bytes, out.payload, lanes, kdata, kt, crc8, crc8b, K,
+               max_its, w_stored, it0, it_end);
   TdecP2ExecGpu ex{(int)(threadIdx.x / LANES), xs};
   const TdecP2Result r = tdec_p2_lane<true, CKS>(a, lane, ex);
   if (ex.wave) return;
-#pragma unroll
-  for (int h = 0; h < 2; h++) {
-    if (!((a.live >> h) & 1u)) continue;
-    out.its[li[h]] = r.its[h];
-    out.crc_ok[li[h]] = r.crc_ok[h];
-    out.tb_part[li[h]] = r.tb_part[h];
-  }
+  p2_put_result(a.live, li, r, out.its, out.crc_ok, out.tb_part);
 }
 
 // 3'. a re-compaction round after the first, segmented (tdec_p2_body.h p2s_*): one workgroup of S wavefronts per dense
@@ -496,37 +422,16 @@ void tdec_kernel_p2s(uint32_t* __restrict__ cscr, uint8_t* __restrict__ cdec, Td
   __shared__ uint32_t vecs[4][S * P2_CKW * LANES];
   const uint32_t n = cont_count(cont, cap), p = blockIdx.x;
   if ((size_t)p * 2 * LANES >= n) return;   // the whole workgroup
-  for (uint32_t b = threadIdx.x; b < 256; b += blockDim.x) {
-    crc8[b] = crc24_byte_entry(b, CRC24A_POLY);
-    crc8b[b] = crc24_byte_entry(b, CRC24B_POLY);
-  }
+  crc24_fill_tables(crc8, crc8b, threadIdx.x, blockDim.x);
   __syncthreads();
   const int lane = threadIdx.x % LANES;
   const uint32_t wave = threadIdx.x / LANES;
-  const uint32_t d0 = p * 2 * LANES + lane, d1 = d0 + LANES;
   TdecArgsP2 a{};
-  a.live = (d0 < n ? 1u : 0u) | (d1 < n ? 2u : 0u);   // dead halves decode zeros, consistently (no early exit: barriers)
-  const uint32_t li[2] = {d0 < n ? cont[1 + d0] : cont[1 + p * 2 * LANES],
-                          d1 < n ? cont[1 + d1] : (d0 < n ? cont[1 + d0] : cont[1 + p * 2 * LANES])};
-  const MiLaneDesc l0 = lanes[li[0]], l1 = lanes[li[1]];
-  a.scr = cscr + (size_t)p * pair_u32;
-  a.q = a.scr + (size_t)(4 * K + 8) * LANES;
-  a.pos = kdata + kt.pos_off;
-  a.pi = kdata + kt.pi_off;
-  a.crc8 = crc8;
-  a.crc8b = crc8b;
-  a.dec = cdec + (size_t)p * dec_stride;
-  p2_out(a, 0, out, li[0], l0);
-  p2_out(a, 1, out, li[1], l1);
-  a.to_payload = out.payload != nullptr;
-  a.K = K;
-  a.F[0] = l0.F;
-  a.F[1] = l1.F;
-  a.max_its = max_its;
-  a.early_stop = 1;
-  a.cont_w = 1;
-  a.it0 = it0;
-  a.it_end = it0 + 1;
+  uint32_t li[2];
+  // dead halves decode zeros, consistently (no early exit: barriers)
+  a.live = p2_cont_lanes<true>(li, cont, n, p, lane);
+  p2_cont_args(a, li, p, cscr, pair_u32, cdec, dec_stride, out.cb_bytes, out.payload, lanes, kdata, kt, crc8, crc8b, K,
+               max_its, 1u, it0, it0 + 1);
   // (built field by field: a const aggregate of LDS addresses becomes a static initializer the backend cannot emit)
   P2SegVecs V;
   V.bvec = vecs[0];
@@ -537,104 +442,82 @@ void tdec_kernel_p2s(uint32_t* __restrict__ cscr, uint8_t* __restrict__ cdec, Td
   p2s_half<false>(a, lane, wave, g, V);
   p2s_half<true>(a, lane, wave, g, V);
   if (wave || !a.live) return;   // wave 0: the check pass over the decision rows and the outputs
-  uint32_t tbp[2] = {0u, 0u};
-  const uint32_t ok = tdec_p2_check(a, lane, a.live, tbp);
-#pragma unroll
-  for (int h = 0; h < 2; h++) {
-    if (!((a.live >> h) & 1u)) continue;
-    out.its[li[h]] = it0 + 1;
-    out.crc_ok[li[h]] = (ok >> h) & 1u;
-    out.tb_part[li[h]] = tbp[h];
-  }
+  p2_put_result(a.live, li, p2s_check(a, lane), out.its, out.crc_ok, out.tb_part);
 }
 
-bool launch_tdec_cont(const float* sb, const uint32_t* wm, float* scratch, size_t scr_pair_u32, uint8_t* dec,
-                      uint8_t* cb_bytes, uint32_t* cb_its, uint32_t* cb_crc, uint32_t* cb_tbp, const MiGroupDesc* groups,
-                      const MiLaneDesc* lanes, const uint32_t* ktab_data, const MiKTab& kt, uint32_t n_groups, uint32_t* cont,
-                      uint32_t* cscr, uint8_t* cdec, uint32_t max_pairs, size_t pair_u32, uint32_t K, uint32_t max_its,
-                      uint32_t gather_wgs, uint8_t* payload, bool w_stored, bool rounds, uint32_t* h_count,
-                      uint32_t seg, bool cont_zeroed, hipStream_t st) {
-  if (!n_groups || !max_pairs) return true;
-  const TdecOut out{cb_bytes, cb_its, cb_crc, cb_tbp, payload};
+bool launch_tdec_cont(const TdecBufs& b, const TdecContBufs& c, const TdecContSched& s, uint32_t n_groups,
+                      const MiKTab& kt, uint32_t K, uint32_t max_its, hipStream_t st) {
+  if (!n_groups || !c.max_pairs) return true;
   const size_t nl = (size_t)n_groups * LANES + 1;   // one list: count + lane indices
-  uint32_t* lists[2] = {cont, cont + nl};
-  uint32_t* src = cont + 2 * nl;
-  if (!cont_zeroed && hipMemsetAsync(cont, 0, 4, st) != hipSuccess) return false;
+  uint32_t* lists[2] = {c.cont, c.cont + nl};
+  uint32_t* src = c.cont + 2 * nl;
+  if (!s.cont_zeroed && hipMemsetAsync(c.cont, 0, 4, st) != hipSuccess) return false;
   const uint32_t cap = n_groups * LANES;
-  hipLaunchKernelGGL(tdec_cont_assign_kernel, dim3(n_groups), dim3(64), 0, st, groups, lanes, cb_crc, cont, cap);
-  if (h_count && hipMemcpyAsync(h_count, cont, 4, hipMemcpyDeviceToHost, st) != hipSuccess) return false;
-  hipLaunchKernelGGL(tdec_cont_gather_kernel, dim3(gather_wgs), dim3(256), 0, st, sb, wm, scratch, groups,
-                     ktab_data + kt.pos_off, cont, cscr, pair_u32, K, (uint32_t)w_stored, cap);
+  hipLaunchKernelGGL(tdec_cont_assign_kernel, dim3(n_groups), dim3(64), 0, st, b.groups, b.lanes, b.out.crc_ok, c.cont,
+                     cap);
+  if (s.h_count && hipMemcpyAsync(s.h_count, c.cont, 4, hipMemcpyDeviceToHost, st) != hipSuccess) return false;
+  hipLaunchKernelGGL(tdec_cont_gather_kernel, dim3(s.gather_wgs), dim3(256), 0, st, b.sb, b.wm, b.scratch, b.groups,
+                     b.kdata + kt.pos_off, c.cont, c.cscr, c.pair_u32, K, (uint32_t)s.w_stored, cap);
+  // iterations it0 .. it_end - 1 of the dense pairs of `list` in `buf`, crossed form
+  auto crossed = [&](auto kernel, uint32_t* buf, size_t stride, uint8_t* dec, size_t dstride, const uint32_t* list,
+                     uint32_t cont_w, uint32_t it0, uint32_t it_end) {
+    hipLaunchKernelGGL(kernel, dim3(c.max_pairs), dim3(128), 0, st, buf, dec, b.out, b.lanes, b.kdata, kt, list, stride,
+                       dstride, K, max_its, cont_w, it0, it_end, cap);
+  };
   const size_t cdec_stride = (size_t)K * LANES;
-  if (!rounds) {   // one launch for iterations 1 .. max_its - 1 (each pair until its slowest code block stops)
-    hipLaunchKernelGGL(tdec_kernel_p2c<P2C_CKS>, dim3(max_pairs), dim3(128), 0, st, cscr, cdec, out, lanes,
-                       ktab_data, kt, cont,
-                       pair_u32, cdec_stride, K, max_its, (uint32_t)w_stored, 1u, max_its, cap);
+  if (!s.rounds) {   // one launch for iterations 1 .. max_its - 1 (each pair until its slowest code block stops)
+    crossed(tdec_kernel_p2c<P2C_CKS>, c.cscr, c.pair_u32, c.cdec, cdec_stride, c.cont, (uint32_t)s.w_stored, 1u,
+            max_its);
     return true;
   }
   // re-compaction: one iteration per round, the code blocks still failing gathered into fewer dense pairs for the
   // next.  The pair buffers alternate between the continuation scratch and the groups' own scratch (free after the
   // first gather; group pair j's region holds dense pair j: 2 (2K + 8 (K/4 + 1)) >= 7K + 20 rows of 64 lanes)
-  uint32_t* bufs[2] = {cscr, reinterpret_cast<uint32_t*>(scratch)};
-  const size_t strides[2] = {pair_u32, scr_pair_u32};
-  uint8_t* decs[2] = {cdec, dec};
+  uint32_t* bufs[2] = {c.cscr, reinterpret_cast<uint32_t*>(b.scratch)};
+  const size_t strides[2] = {c.pair_u32, c.scr_pair_u32};
+  uint8_t* decs[2] = {c.cdec, b.dec};
   const size_t dstrides[2] = {cdec_stride, 2 * cdec_stride};
+  // the late rounds segmented: S wavefronts per pair
+  auto segmented = [&](auto kernel, uint32_t S, int i, const uint32_t* list, uint32_t it) {
+    hipLaunchKernelGGL(kernel, dim3(c.max_pairs), dim3(64 * S), 0, st, bufs[i], decs[i], b.out, b.lanes, b.kdata, kt,
+                       list, strides[i], dstrides[i], K, max_its, it, cap);
+  };
   for (uint32_t it = 1; it < max_its; it++) {
-    const int b = (int)((it - 1) & 1u), l = b;
+    const int i = (int)((it - 1) & 1u), l = i;
     if (it > 1) {
       if (hipMemsetAsync(lists[l], 0, 4, st) != hipSuccess) return false;
-      hipLaunchKernelGGL(tdec_cont_assign2_kernel, dim3(2 * max_pairs), dim3(64), 0, st, lists[l ^ 1], cb_crc, lists[l],
-                         src, cap);
-      hipLaunchKernelGGL(tdec_cont_gather2_kernel, dim3(gather_wgs), dim3(256), 0, st, bufs[b ^ 1], strides[b ^ 1],
-                         lists[l], src, bufs[b], strides[b], K, cap);
+      hipLaunchKernelGGL(tdec_cont_assign2_kernel, dim3(2 * c.max_pairs), dim3(64), 0, st, lists[l ^ 1], b.out.crc_ok,
+                         lists[l], src, cap);
+      hipLaunchKernelGGL(tdec_cont_gather2_kernel, dim3(s.gather_wgs), dim3(256), 0, st, bufs[i ^ 1], strides[i ^ 1],
+                         lists[l], src, bufs[i], strides[i], K, cap);
     }
     // each round's count, for the next run's grids (h_count[it - 1]: the list this round decodes)
-    if (it > 1 && h_count && it <= CONT_HIST &&
-        hipMemcpyAsync(h_count + it - 1, lists[l], 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+    if (it > 1 && s.h_count && it <= CONT_HIST &&
+        hipMemcpyAsync(s.h_count + it - 1, lists[l], 4, hipMemcpyDeviceToHost, st) != hipSuccess)
       return false;
-    if (it > 1 && seg == 8)   // the late rounds segmented: seg wavefronts per pair (tdec_kernel_p2s)
-      hipLaunchKernelGGL(tdec_kernel_p2s<8>, dim3(max_pairs), dim3(512), 0, st, bufs[b], decs[b], out, lanes, ktab_data,
-                         kt, lists[l], strides[b], dstrides[b], K, max_its, it, cap);
-    else if (it > 1 && seg == 4)
-      hipLaunchKernelGGL(tdec_kernel_p2s<4>, dim3(max_pairs), dim3(256), 0, st, bufs[b], decs[b], out, lanes, ktab_data,
-                         kt, lists[l], strides[b], dstrides[b], K, max_its, it, cap);
+    if (it > 1 && s.seg == 8) segmented(tdec_kernel_p2s<8>, 8, i, lists[l], it);
+    else if (it > 1 && s.seg == 4) segmented(tdec_kernel_p2s<4>, 4, i, lists[l], it);
     else if (it > 1)
-      hipLaunchKernelGGL(tdec_kernel_p2c<P2C_CKS_LATE>, dim3(max_pairs), dim3(128), 0, st, bufs[b], decs[b], out, lanes,
-                         ktab_data, kt, lists[l], strides[b], dstrides[b], K, max_its, 1u, it, it + 1, cap);
+      crossed(tdec_kernel_p2c<P2C_CKS_LATE>, bufs[i], strides[i], decs[i], dstrides[i], lists[l], 1u, it, it + 1);
     else
-      hipLaunchKernelGGL(tdec_kernel_p2c<P2C_CKS>, dim3(max_pairs), dim3(128), 0, st, bufs[b], decs[b], out,
-                         lanes, ktab_data, kt, lists[l], strides[b], dstrides[b], K, max_its,
-                         (uint32_t)(w_stored || it > 1), it, it + 1, cap);
+      crossed(tdec_kernel_p2c<P2C_CKS>, bufs[i], strides[i], decs[i], dstrides[i], lists[l], (uint32_t)s.w_stored, it,
+              it + 1);
   }
   return true;
 }
 
-void launch_tdec(const float* sb, const uint32_t* wm, float* scratch, uint8_t* dec, uint8_t* cb_bytes, uint32_t* cb_its, uint32_t* cb_crc,
-                 uint32_t* cb_tbp, const MiGroupDesc* groups, const MiLaneDesc* lanes, const MiKTab* ktabs,
-                 const uint32_t* ktab_data, uint32_t n_groups, uint32_t max_its, uint32_t early_stop, bool q16,
-                 int crossed, hipStream_t st) {
+void launch_tdec(const TdecBufs& b, uint32_t n_groups, uint32_t max_its, uint32_t early_stop, bool q16, int crossed,
+                 hipStream_t st) {
   if (!n_groups) return;
-  const TdecOut out{cb_bytes, cb_its, cb_crc, cb_tbp, nullptr};
-  if (crossed == 2 && q16) {
-    hipLaunchKernelGGL(tdec_kernel_i16xr, dim3(n_groups), dim3(128), 0, st, sb, wm, scratch, dec, out, groups, lanes,
-                       ktabs, ktab_data, max_its, early_stop);
-    return;
-  }
-  if (crossed) {
-    if (q16)
-      hipLaunchKernelGGL(tdec_kernel_i16x, dim3(n_groups), dim3(128), 0, st, sb, wm, scratch, dec, out, groups, lanes,
-                         ktabs, ktab_data, max_its, early_stop);
-    else
-      hipLaunchKernelGGL(tdec_kernel_genx, dim3(n_groups), dim3(128), 0, st, sb, wm, scratch, dec, out, groups, lanes,
-                         ktabs, ktab_data, max_its, early_stop);
-    return;
-  }
-  if (q16)
-    hipLaunchKernelGGL(tdec_kernel_i16, dim3(n_groups), dim3(64), 0, st, sb, wm, scratch, dec, out, groups, lanes, ktabs,
-                       ktab_data, max_its, early_stop);
-  else
-    hipLaunchKernelGGL(tdec_kernel_gen, dim3(n_groups), dim3(64), 0, st, sb, wm, scratch, dec, out, groups, lanes, ktabs,
-                       ktab_data, max_its, early_stop);
+  TdecOut out = b.out;
+  out.payload = nullptr;   // the lane forms write code-block rows
+  auto go = [&](auto kernel, uint32_t threads) {
+    hipLaunchKernelGGL(kernel, dim3(n_groups), dim3(threads), 0, st, b.sb, b.wm, b.scratch, b.dec, out, b.groups,
+                       b.lanes, b.ktabs, b.kdata, max_its, early_stop);
+  };
+  if (crossed == 2 && q16) go(tdec_kernel_i16xr, 128);
+  else if (crossed) go(q16 ? tdec_kernel_i16x : tdec_kernel_genx, 128);
+  else go(q16 ? tdec_kernel_i16 : tdec_kernel_gen, 64);
 }
 
 }  // namespace mi

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "dl_common.h"
+#include "kernels_consts.h"
 
 #ifndef MI_HD
 #define MI_HD __host__ __device__
@@ -69,6 +70,46 @@ struct TdecArgs {
 // the code block's own CRC register, accumulated by linearity during DEC2's forward pass (early stop)
 struct TdecCrc { uint32_t cb; };
 struct TdecLaneResult { uint32_t its; uint32_t crc_ok; uint32_t tb_part; };
+
+// The turbo stage's buffers as one work item addresses them: on the GPU the decoder kernels' pointer parameters
+// (kernels.h TdecBufs, unpacked by the launchers), in emu.cpp host arrays.  The per-work-item setup below and in
+// tdec_p2_body.h is the code both run.  It takes the descriptors (MiGroupDesc, MiKTab, MiLaneDesc) already loaded: the
+// kernels load them through their own __restrict__ parameters, which is what keeps those loads scalar and the hot
+// kernels' register counts where they are.
+struct TdecMem {
+  const float* sb;        // softbuffer arena (MiGroupDesc::sb_off)
+  const uint32_t* wm;     // window masks, WM_STRIDE words per group
+  float* scratch;         // MiGroupDesc::scratch_off
+  uint8_t* dec;           // MiGroupDesc::dec_off
+  uint8_t* cb_bytes;      // [lane index][CB_BYTES_STRIDE] output rows
+  uint8_t* payload;       // packed decoder: the TB payload buffer its runs go to, nullptr = the rows
+  const uint32_t* kdata;  // the per-K tables (MiKTab offsets)
+};
+
+// the lane-form decoders' work item (tdec.hip tdec_group: one wavefront, or two crossed, per group): the valid lane
+// with lane index li and descriptor ld of group gi (g, its tables kt)
+MI_HD __attribute__((always_inline)) inline void tdec_lane_args(TdecArgs& a, const TdecMem& m, uint32_t gi,
+                                                                const MiGroupDesc& g, const MiKTab& kt, uint32_t li,
+                                                                const MiLaneDesc& ld, const uint32_t* crc8,
+                                                                uint32_t max_its, uint32_t early_stop) {
+  a.sb = m.sb + g.sb_off;
+  a.wm = m.wm + (size_t)gi * WM_STRIDE;
+  a.zrow = g.Ncb;
+  a.q16 = reinterpret_cast<int16_t*>(m.scratch + g.scratch_off) + q16_elem_off(g.K);
+  a.pos = m.kdata + kt.pos_off;
+  a.pi = m.kdata + kt.pi_off;
+  a.crc_a = m.kdata + kt.crca_off;
+  a.crc_b = m.kdata + kt.crcb_off;
+  a.crc8 = crc8;
+  a.scr = m.scratch + g.scratch_off;
+  a.dec = m.dec + g.dec_off;
+  a.cb_bytes = m.cb_bytes + (size_t)li * CB_BYTES_STRIDE;
+  a.K = g.K;
+  a.F = ld.F;
+  a.max_its = max_its;
+  a.early_stop = early_stop;
+  a.crc24a = ld.crc24a;
+}
 
 
 // The trellis steps below are generic over the metric type T: float (both scalar decoders: the float

@@ -38,6 +38,9 @@
 // The DEC2 passes carry each step's interleaver index pi(k) from the window's loads to its stores in
 // scalar registers (TdecWinP2::pk): no table load, and no wait on one, between a step's arithmetic and
 // its outputs.
+//
+// The per-work-item setup (p2_first_args, p2_cont_lanes, p2_cont_args, p2_out, p2_put_result, p2_cont_src*) lives here
+// too, so the kernels of tdec.hip and the CPU emulation (emu.cpp) run one copy of its pointer and offset arithmetic.
 #pragma once
 #include "tdec_body.h"
 
@@ -79,6 +82,116 @@ struct TdecP2Result { uint32_t its[2], crc_ok[2], tb_part[2]; };
 // pointer before the buffer is ever formed
 MI_HD inline int64_t p2_run_off(const TdecArgsP2& a, int h) {
   return (int64_t)a.cb_off[h] - (int64_t)(a.to_payload ? a.F[h] / 8 : 0u);
+}
+
+// ---- per-work-item setup: the code tdec.hip's kernels and emu.cpp both run (TdecMem: tdec_body.h) --------------
+// the output of half h: code block li's payload run (payload non-null: MiLaneDesc pay_st), or its row of cb_bytes;
+// crc24a bit 1 = the code block carries the TB CRC (tdec_p2_check)
+MI_P2_INL void p2_out(TdecArgsP2& a, int h, uint8_t* cb_bytes, uint8_t* payload, uint32_t li, const MiLaneDesc& ld) {
+  a.out_bytes = payload ? payload : cb_bytes;
+  a.cb_off[h] = payload ? ld.pay_st : li * CB_BYTES_STRIDE;
+  a.crc24a[h] = ld.crc24a | (ld.tbcrc << 1);
+}
+// The first launch's work item is one lane of a pair: group ga and group gbi (0xFFFFFFFF = unpaired, the high halves
+// carry no code block); gA, gB = their descriptors (gB = gA if unpaired), kt = gA's tables, li / l0, l1 = the halves'
+// lane indices and descriptors.  p2_first_live: its live halves; 0 = it holds no code block (the same on both
+// wavefronts of the pair) and decodes nothing.
+MI_P2_INL uint32_t p2_first_live(uint32_t gbi, const MiLaneDesc& l0, const MiLaneDesc& l1) {
+  return (l0.valid ? 1u : 0u) | (gbi != 0xFFFFFFFFu && l1.valid ? 2u : 0u);
+}
+// p2_first_args: its arguments (a.live = p2_first_live, non-zero).  A dead half decodes a copy of half 0's routing
+// and writes nothing.  emu.cpp calls this; tdec_kernel_p2x spells the same statements out in its body, because its
+// register allocation (the trellis loops' VGPR numbering, 144 VGPRs in the one-iteration form) does not survive the
+// function boundary -- a change here is a change there.
+MI_P2_INL void p2_first_args(TdecArgsP2& a, const TdecMem& m, uint32_t ga, uint32_t gbi, const MiGroupDesc& gA,
+                             const MiGroupDesc& gB, const MiKTab& kt, const uint32_t (&li)[2], const MiLaneDesc& l0,
+                             const MiLaneDesc& l1, const uint32_t* crc8, const uint32_t* crc8b, uint32_t max_its,
+                             uint32_t early_stop, uint32_t no_w) {
+  const bool paired = gbi != 0xFFFFFFFFu;
+  const uint32_t gb = paired ? gbi : ga;
+  a.sb[0] = m.sb + gA.sb_off;
+  a.sb[1] = m.sb + gB.sb_off;
+  a.wm[0] = m.wm + (size_t)ga * WM_STRIDE;
+  a.wm[1] = m.wm + (size_t)gb * WM_STRIDE;
+  a.zrow[0] = gA.Ncb;
+  a.zrow[1] = gB.Ncb;
+  const uint32_t K = gA.K;
+  a.scr = reinterpret_cast<uint32_t*>(m.scratch + gA.scratch_off);   // spans both groups' scratch (plan.cpp)
+  a.q = a.scr + (size_t)(4 * K + 8) * LANES;   // the pair scratch layout: w rows at 0, q rows at 4K + 8 rows
+  a.pos = m.kdata + kt.pos_off;
+  a.pi = m.kdata + kt.pi_off;
+  a.crc8 = crc8;
+  a.crc8b = crc8b;
+  a.dec = m.dec + gA.dec_off;
+  p2_out(a, 0, m.cb_bytes, m.payload, li[0], l0);
+  if (a.live & 2u) p2_out(a, 1, m.cb_bytes, m.payload, li[1], l1);
+  else p2_out(a, 1, m.cb_bytes, m.payload, li[0], l0);
+  a.to_payload = m.payload != nullptr;
+  a.K = K;
+  a.F[0] = l0.F;
+  a.F[1] = paired ? l1.F : l0.F;
+  a.max_its = max_its;
+  a.early_stop = early_stop;
+  a.cont_w = 0;
+  a.no_w = no_w;   // a one-iteration first launch whose continuation re-forms the w rows (launch_tdec_p2)
+}
+// Dense continuation pair p of a list (cont[0] = its count, clamped by the caller to n; cont[1 ..] = lane indices):
+// half h of lane `lane` holds cont[1 + 128 p + 64 h + lane].  Returns the live halves (half 1 is live only if half 0 is)
+// and their lane indices li; callers skip pairs with 128 p >= n.  A dead half takes the lane's half 0's index.
+// DEAD_LANES: the caller also decodes lanes without any code block (tdec_kernel_p2s: every lane joins its barriers);
+// they take the pair's first entry, so they decode valid descriptors, consistently on every wavefront, and write
+// nothing.  Otherwise li is unset when 0 is returned.
+template <bool DEAD_LANES>
+MI_P2_INL uint32_t p2_cont_lanes(uint32_t (&li)[2], const uint32_t* cont, uint32_t n, uint32_t p, int lane) {
+  const uint32_t d0 = p * 2 * LANES + lane, d1 = d0 + LANES;
+  const uint32_t live = (d0 < n ? 1u : 0u) | (d1 < n ? 2u : 0u);
+  if constexpr (DEAD_LANES) {
+    li[0] = d0 < n ? cont[1 + d0] : cont[1 + p * 2 * LANES];
+    li[1] = d1 < n ? cont[1 + d1] : (d0 < n ? cont[1 + d0] : cont[1 + p * 2 * LANES]);
+  } else {
+    if (!live) return 0u;
+    li[0] = cont[1 + d0];
+    li[1] = (live & 2u) ? cont[1 + d1] : cont[1 + d0];
+  }
+  return live;
+}
+// the continuation's work item (a.live, li: p2_cont_lanes): iterations it0 .. it_end - 1 of dense pair p, whose state
+// the gather put at cscr + p pair_u32 and whose decision rows are at cdec + p dec_stride
+MI_P2_INL void p2_cont_args(TdecArgsP2& a, const uint32_t (&li)[2], uint32_t p, uint32_t* cscr, size_t pair_u32,
+                            uint8_t* cdec, size_t dec_stride, uint8_t* cb_bytes, uint8_t* payload,
+                            const MiLaneDesc* lanes, const uint32_t* kdata, const MiKTab& kt, const uint32_t* crc8,
+                            const uint32_t* crc8b, uint32_t K, uint32_t max_its, uint32_t cont_w, uint32_t it0,
+                            uint32_t it_end) {
+  const MiLaneDesc l0 = lanes[li[0]], l1 = lanes[li[1]];
+  a.scr = cscr + (size_t)p * pair_u32;
+  a.q = a.scr + (size_t)(4 * K + 8) * LANES;
+  a.pos = kdata + kt.pos_off;
+  a.pi = kdata + kt.pi_off;
+  a.crc8 = crc8;
+  a.crc8b = crc8b;
+  a.dec = cdec + (size_t)p * dec_stride;
+  p2_out(a, 0, cb_bytes, payload, li[0], l0);
+  p2_out(a, 1, cb_bytes, payload, li[1], l1);
+  a.to_payload = payload != nullptr;
+  a.K = K;
+  a.F[0] = l0.F;
+  a.F[1] = l1.F;
+  a.max_its = max_its;
+  a.early_stop = 1;
+  a.cont_w = cont_w;
+  a.it0 = it0;
+  a.it_end = it_end;
+}
+// the live halves' results to the per-code-block outputs (on the GPU: by the wavefront that ran tdec_p2_check)
+MI_P2_INL void p2_put_result(uint32_t live, const uint32_t (&li)[2], const TdecP2Result& r, uint32_t* its,
+                             uint32_t* crc_ok, uint32_t* tb_part) {
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    if (!((live >> h) & 1u)) continue;
+    its[li[h]] = r.its[h];
+    crc_ok[li[h]] = r.crc_ok[h];
+    tb_part[li[h]] = r.tb_part[h];
+  }
 }
 
 // decoder-input quantiser q(x) = clamp(rint(32 x), +-511) of two floats, packed.  Device: fma(x, 32,
@@ -1259,6 +1372,28 @@ struct P2ContSrc {
   const uint32_t* scr;  // the scratch of the group's pair (w rows: packed, this code block = half hs)
   uint32_t ls, hs;      // lane in the group, half in the pair
 };
+// the first gather's source of the code block with lane index li (plan.cpp: group g = lanes 64 g .. 64 g + 63), whose
+// group is half hs of the first launch's pair with first group ga (the owner of the pair's scratch)
+MI_P2_INL P2ContSrc p2_cont_src(const float* sb, const uint32_t* wm, const float* scratch, const MiGroupDesc* groups,
+                                   uint32_t li, uint32_t ga, uint32_t hs) {
+  const uint32_t g = li / LANES;
+  P2ContSrc s;
+  s.sb = sb + groups[g].sb_off;
+  s.wm = wm + (size_t)g * WM_STRIDE;
+  s.scr = reinterpret_cast<const uint32_t*>(scratch + groups[ga].scratch_off);
+  s.ls = li % LANES;
+  s.hs = hs;
+  return s;
+}
+// a re-compaction round's source: slot e of the previous round's list = its dense pair e / 128 (pair stride prev_u32
+// words from prev), half (e / 64) % 2, lane e % 64; only packed rows are gathered (no softbuffer, no masks)
+MI_P2_INL P2ContSrc p2_cont_src2(const uint32_t* prev, size_t prev_u32, uint32_t e) {
+  P2ContSrc s = {};
+  s.scr = prev + (size_t)(e / (2 * LANES)) * prev_u32;
+  s.ls = e % LANES;
+  s.hs = (e / LANES) & 1u;
+  return s;
+}
 MI_HD inline uint32_t p2_cont_qwins(uint32_t K) { return K / BETA_W + 1; }   // 3 (K + 4) q rows, incl. the tail
 // q rows 12 w .. 12 w + 11 of one continuation lane (both halves), packed
 MI_HD inline void p2_cont_qwin(const P2ContSrc (&s)[2], uint32_t live, const uint32_t* pos, uint32_t w,
@@ -1489,6 +1624,18 @@ inline void p2s_half_host(const TdecArgsP2& a, int lane, uint32_t S, const P2Seg
     for (uint32_t j = 1; j < nseg; j++) p2s_vld(V.aend, j - 1, lane, na[j]);
     for (uint32_t j = 1; j < nseg; j++) ch = p2s_fwd_fix<DEC2>(a, lane, p2s_seg(a.K, S, j), V, na[j]) || ch;
   }
+}
+// a segmented round's one iteration (a.it0) ends as tdec_p2_lane's do: the check pass over the decision rows and the
+// outputs of the live halves (GPU: wavefront 0, after both constituent decoders)
+MI_P2_INL TdecP2Result p2s_check(const TdecArgsP2& a, int lane) {
+  TdecP2Result r = {};
+  const uint32_t ok = tdec_p2_check(a, lane, a.live, r.tb_part);
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    r.its[h] = a.it0 + 1;
+    r.crc_ok[h] = (ok >> h) & 1u;
+  }
+  return r;
 }
 
 struct TdecP2ExecHost {

@@ -7,13 +7,6 @@
 
 namespace mi {
 
-struct TdecWinOut {
-  uint8_t* cb_bytes;
-  uint32_t* its;
-  uint32_t* crc_ok;
-  uint32_t* tb_part;
-};
-
 template <int P>
 __device__ __forceinline__ uint32_t block_xor(uint32_t v, uint32_t* red) {
 #pragma unroll
@@ -54,7 +47,7 @@ __device__ __forceinline__ void win_half(const WinCb& c, uint32_t t) {
 }
 
 template <int P>
-__global__ __launch_bounds__(P) void tdec_win_kernel(const float* __restrict__ sb, TdecWinOut out,
+__global__ __launch_bounds__(P) void tdec_win_kernel(const float* __restrict__ sb, TdecOut out,
                                                      const MiGroupDesc* __restrict__ groups,
                                                      const MiLaneDesc* __restrict__ lanes,
                                                      const MiKTab* __restrict__ ktabs,
@@ -83,7 +76,7 @@ __global__ __launch_bounds__(P) void tdec_win_kernel(const float* __restrict__ s
   c.bend = reinterpret_cast<int16_t*>(p); p += P * 16;
   c.aend = reinterpret_cast<int16_t*>(p);
   c.lmap = reinterpret_cast<uint8_t*>(c.bck);   // bck + ack: 2 (K/4 + 1) 16 bytes >= Ncb rounded to 16
-  for (uint32_t b = t; b < 256; b += P) crc8[b] = crc24_byte_entry(b, CRC24A_POLY);
+  crc24_fill_tables(crc8, t, P);
   win_load_map(c, t, P, sb + g.sb_off, g.Ncb);
   __syncthreads();
   win_load(c, t, P, sb + g.sb_off, kdata + kt.pos_off, kdata + kt.pi_off, li % LANES, ld.F);
@@ -115,9 +108,8 @@ __global__ __launch_bounds__(P) void tdec_win_kernel(const float* __restrict__ s
 }
 
 template <int P>
-static void launch_win_p(const float* sb, const TdecWinOut& out, const MiGroupDesc* groups, const MiLaneDesc* lanes,
-                         const MiKTab* ktabs, const uint32_t* kdata, uint32_t n_lanes, uint32_t max_k,
-                         uint32_t max_its, uint32_t early_stop, hipStream_t st) {
+static void launch_win_p(const TdecBufs& b, uint32_t n_lanes, uint32_t max_k, uint32_t max_its, uint32_t early_stop,
+                         hipStream_t st) {
   const uint32_t lds = win_lds_bytes(max_k, P);
   static bool attr = false;   // idempotent; the attribute is per function
   if (!attr) {
@@ -125,24 +117,17 @@ static void launch_win_p(const float* sb, const TdecWinOut& out, const MiGroupDe
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_lds_bytes(KMAX, P));
     attr = true;
   }
-  hipLaunchKernelGGL(tdec_win_kernel<P>, dim3(n_lanes), dim3(P), lds, st, sb, out, groups, lanes, ktabs, kdata, max_its,
-                     early_stop);
+  hipLaunchKernelGGL(tdec_win_kernel<P>, dim3(n_lanes), dim3(P), lds, st, b.sb, b.out, b.groups, b.lanes, b.ktabs,
+                     b.kdata, max_its, early_stop);
 }
 
-void launch_tdec_win(const float* sb, uint8_t* cb_bytes, uint32_t* cb_its, uint32_t* cb_crc, uint32_t* cb_tbp,
-                     const MiGroupDesc* groups, const MiLaneDesc* lanes, const MiKTab* ktabs, const uint32_t* kdata,
-                     uint32_t n_lanes, uint32_t max_k, uint32_t max_its, uint32_t early_stop, uint32_t threads,
-                     hipStream_t st) {
+void launch_tdec_win(const TdecBufs& b, uint32_t n_lanes, uint32_t max_k, uint32_t max_its, uint32_t early_stop,
+                     uint32_t threads, hipStream_t st) {
   if (!n_lanes) return;
-  const TdecWinOut out{cb_bytes, cb_its, cb_crc, cb_tbp};
-  if (threads <= 64)
-    launch_win_p<64>(sb, out, groups, lanes, ktabs, kdata, n_lanes, max_k, max_its, early_stop, st);
-  else if (threads <= 128)
-    launch_win_p<128>(sb, out, groups, lanes, ktabs, kdata, n_lanes, max_k, max_its, early_stop, st);
-  else if (threads <= 256)
-    launch_win_p<256>(sb, out, groups, lanes, ktabs, kdata, n_lanes, max_k, max_its, early_stop, st);
-  else
-    launch_win_p<512>(sb, out, groups, lanes, ktabs, kdata, n_lanes, max_k, max_its, early_stop, st);
+  if (threads <= 64) launch_win_p<64>(b, n_lanes, max_k, max_its, early_stop, st);
+  else if (threads <= 128) launch_win_p<128>(b, n_lanes, max_k, max_its, early_stop, st);
+  else if (threads <= 256) launch_win_p<256>(b, n_lanes, max_k, max_its, early_stop, st);
+  else launch_win_p<512>(b, n_lanes, max_k, max_its, early_stop, st);
 }
 
 }  // namespace mi
