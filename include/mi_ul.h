@@ -34,7 +34,14 @@
  * bandwidth, the frequency position (with frequency hopping), the base sequence and the cyclic shift of one
  * transmission, mi_srs_batch_* plans N transmissions once and encodes them per call into device-resident SC-FDMA IQ
  * with the layout and normalisation of the PUSCH batch: symbols 0..12 zero, the SRS in symbol 13.  Limits: FDD,
- * normal CP, one antenna port, no aperiodic SRS.  PUSCH is not shortened in cell-specific SRS subframes.
+ * normal CP, one antenna port, no aperiodic SRS.
+ *
+ * PUSCH in SRS subframes (36.211 5.3.4, 36.212 5.2.2.6-5.2.2.8): mi_ul_cfg_t.n_srs = 1 shortens the transmission to 11
+ * data symbols (rate matching, UCI multiplexing and an 11-column channel interleaver follow; symbol 13 is written as
+ * zeros), n_symb_initial carries the first transmission's symbol count into a retransmission's Q' formulas.
+ * mi_ul_pusch_n_srs decides n_srs from the cell's SRS configuration and the PRBs, mi_ul_pusch_resource reports what
+ * the planner derives.  A MI_SRS_FLAG_LAST_SYMBOL_ONLY SRS batch run after the PUSCH batch on the same stream puts
+ * the UE's own SRS into the freed symbol.  Limits: M_sc^PUSCH-initial = the current M, normal CP, FDD (no UpPTS).
  *
  * Open-loop UL power control (36.213 5.1): mi_ul_pusch_power, mi_ul_pucch_power, mi_ul_srs_power, host only, at the
  * end of this header.  Limit: no TPC accumulation (f(i) = g(i) = 0).
@@ -44,7 +51,8 @@
  *   srslte_ue_ul_srs_power(&ue_ul, PL)                      :652 -> mi_ue_ul_srs_power     (mi_ul_srs_power)
  *   srslte_ue_ul_pusch_power(&ue_ul, PL, p0_preamble)       :568 -> mi_ue_ul_pusch_power   (mi_ul_pusch_power)
  *   srslte_ue_ul_pucch_power(&ue_ul, PL, format, n_cqi, n_harq) :622 -> mi_ue_ul_pucch_power (mi_ul_pucch_power)
- * srsUE's own flow never sends the SRS together with PUSCH or PUCCH in one subframe.
+ * srsUE's own flow never sends the SRS together with PUCCH in one subframe; with mi_ue_ul_set_pusch_srs the PUSCH
+ * encode call shortens the PUSCH in SRS subframes and lays the UE's own SRS into the freed symbol.
  */
 #ifndef MI_UL_H
 #define MI_UL_H
@@ -68,7 +76,36 @@ typedef struct {
                                                           index 2..15 (36.213 Table 8.6.3-3) */
   uint8_t  cqi[64];                                    /* CQI bits o_0 .. o_{O-1}, one per byte (srslte_uci_data_t) */
   uint32_t ri_len, ri, I_offset_ri;                    /* RI on PUSCH: 0..2 bits (bit 0 = o0), index 0..12 (8.6.3-2) */
+  uint32_t n_srs;                                      /* 1: the last SC-FDMA symbol carries no PUSCH (a cell-specific
+                                                          SRS subframe, 36.211 5.3.4): 11 data symbols, symbol 13
+                                                          written as zeros.  mi_ul_pusch_n_srs decides it */
+  uint32_t n_symb_initial;                             /* N_symb^PUSCH-initial of the TB's first transmission in the
+                                                          Q' formulas (36.212 5.2.2.6): 11, 12, or 0 = 12 - n_srs */
 } mi_ul_cfg_t;
+
+/* what the planner derives for one transmission (36.212 5.2.2.6-5.2.2.8), and what the CPU tests compare */
+typedef struct {
+  uint32_t n_symb;                      /* data symbols of the subframe, 12 - n_srs */
+  uint32_t G;                           /* UL-SCH coded bits: (n_symb M - Q'_CQI - Q'_RI) Qm */
+  uint32_t q_ack, q_ri, q_cqi;          /* Q'_ACK, Q'_RI, Q'_CQI coded symbols */
+  uint32_t C;                           /* code blocks */
+  uint32_t E[16];                       /* rate-matching output bits of code blocks 0 .. C - 1 (5.1.4.1.2) */
+} mi_ul_res_t;
+/* host only (no device needed).  Every field of *c is checked first: 0, or -1 + mi_last_error with *r untouched.
+ * mi_ul_batch_create plans through the same code.  Rejected (the error text begins "PUSCH"): n_srs > 1,
+ * n_symb_initial outside {0, 11, 12}, UCI that leaves no cell for the data */
+int mi_ul_pusch_resource(const mi_ul_cfg_t *c, mi_ul_res_t *r);
+
+/* Is the PUSCH of this subframe shortened by one symbol (36.211 5.3.4)?  The cell's srs-SubframeConfig (0..14) and
+ * srs-BandwidthConfig (0..7), the subframe, the first PRB of the allocation in slots 0 / 1 and its length,
+ * ue_sends_srs = this UE sends its own SRS in the subframe.  Returns 0, 1, or -1 for bad arguments.
+ *   MI_PUSCH_SRS_OVERLAP  1 if ue_sends_srs, or if the subframe is cell-specific SRS and the PRBs of either slot meet
+ *                         the cell's sounding band [floor(N_RB / 2) - m_SRS,0 / 2, ... + m_SRS,0) (5.5.3.2)
+ *   MI_PUSCH_SRS_ALL_CS   1 in every cell-specific SRS subframe and if ue_sends_srs (srsLTE's rule, for eNBs built on it)
+ *   MI_PUSCH_SRS_OFF      always 0 */
+enum { MI_PUSCH_SRS_OFF = 0, MI_PUSCH_SRS_OVERLAP, MI_PUSCH_SRS_ALL_CS };
+int mi_ul_pusch_n_srs(uint32_t nof_prb, uint32_t srs_subframe_config, uint32_t srs_bw_cfg, uint32_t sf_idx,
+                      uint32_t n_prb0, uint32_t n_prb1, uint32_t L_prb, int ue_sends_srs, uint32_t rule);
 
 enum { MI_UL_STAGE_CRC = 0, MI_UL_STAGE_ENCODE, MI_UL_STAGE_MOD, MI_UL_NSTAGES };
 #define MI_UL_FLAG_PROFILE 1u
@@ -88,7 +125,7 @@ uint32_t mi_ul_batch_n_codeblocks(const mi_ul_batch_t *b);
 int    mi_ul_batch_run(mi_ul_batch_t *b, const void *d_payload, void *d_iq, void *stream);
 /* parity hooks: the coded symbols of transmission i after the last run in channel-interleaver input order
  * (36.212 5.2.2.7 g: Q'_CQI CQI symbols, then the rate-matched data), Qm bits per byte, first bit = MSB;
- * 12 M bytes are written, of which the last Q'_RI (the RI cells) are zero */
+ * n_symb M bytes are written (n_symb = 12 - n_srs), of which the last Q'_RI (the RI cells) are zero */
 int    mi_ul_batch_symbols(mi_ul_batch_t *b, uint32_t i, uint8_t *host);
 int    mi_ul_batch_stage_ms(mi_ul_batch_t *b, float *ms /* MI_UL_NSTAGES */, uint32_t *nruns);
 void   mi_ul_batch_profile_reset(mi_ul_batch_t *b);
@@ -252,6 +289,10 @@ typedef struct {                        /* the fields of srslte_ue_ul_powerctrl_
  * 10 log10(2^(1.25 BPRE) - 1), BPRE = sum_Kr / (144 L_prb) (sum_Kr: the code-block sizes of the TB in bits; 12
  * data symbols), when delta_mcs_based, else 0 */
 float mi_ul_pusch_power(const mi_ul_power_cfg_t *p, float PL, float p0_preamble, uint32_t L_prb, uint32_t sum_Kr);
+/* the same with N_RE = 12 L_prb n_symb_initial (11 when the TB's first transmission was shortened for the SRS);
+ * mi_ul_pusch_power is this at n_symb_initial = 12.  0 for n_symb_initial = 0 */
+float mi_ul_pusch_power_nsymb(const mi_ul_power_cfg_t *p, float PL, float p0_preamble, uint32_t L_prb, uint32_t sum_Kr,
+                              uint32_t n_symb_initial);
 /* P_PUCCH = p0_nominal_pucch + p0_ue_pucch + PL + h(n_cqi, n_harq) + Delta_F(format).  format: MI_PUCCH_*; h =
  * 10 log10(n_cqi / 4) for formats 2/2a/2b with n_cqi >= 4, else 0 (normal CP) */
 float mi_ul_pucch_power(const mi_ul_power_cfg_t *p, float PL, uint32_t format, uint32_t n_cqi, uint32_t n_harq);

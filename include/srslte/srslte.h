@@ -287,8 +287,8 @@ SRSLTE_API void srslte_vec_free(void *ptr);
  * CQI (uci_cqi / uci_cqi_len, up to 64 bits: the (32, O) block code up to 11 bits, CRC8 + tail-biting
  * convolutional code above) and RI (uci_ri / uci_ri_len, 1 or 2 bits).  Limits: PUSCH hopping type 1 only (36.213 8.4.1: DCI format 0 hopping
  * bits through srslte_dci_msg_to_ul_grant's n_rb_ho, intra- or inter-subframe mode from set_cfg's hopping
- * configuration; type 2 returns SRSLTE_ERROR), L_prb >= 3; PUSCH is not
- * shortened in cell-specific SRS subframes.  PUCCH formats 1/1a/1b and 2/2a/2b, the SRS and open-loop UL power
+ * configuration; type 2 returns SRSLTE_ERROR), L_prb >= 3.  In SRS subframes the PUSCH is shortened to 11
+ * data symbols under the rule of mi_ue_ul_set_pusch_srs below (off by default).  PUCCH formats 1/1a/1b and 2/2a/2b, the SRS and open-loop UL power
  * control are available under the library's own names, mi_ue_ul_pucch_encode, mi_ue_ul_srs_encode and
  * mi_ue_ul_*_power below (and as mi_pucch_*, mi_srs_*, mi_ul_*_power in mi_ul.h).  set_cfg keeps every
  * configuration it is given.  set_normalization(true) scales by nof_prb / (15 sqrt(L_prb)) (srsLTE's factor as recorded
@@ -366,6 +366,7 @@ typedef struct SRSLTE_API {
   uint8_t **buffer_b;     /* kept for layout compatibility; NULL */
   void *dev;              /* device copy of the last new-data TB (a retransmission re-encodes it) */
   uint32_t tbs;           /* bits of that TB, 0 = none */
+  uint32_t n_symb_initial; /* data symbols (11 / 12) of that TB's rv 0 transmission: a retransmission's Q' formulas */
 } srslte_softbuffer_tx_t;
 typedef struct SRSLTE_API {
   srslte_cbsegm_t cb_segm;
@@ -409,6 +410,19 @@ SRSLTE_API int srslte_ue_ul_cfg_grant(srslte_ue_ul_t *q, srslte_ra_ul_grant_t *g
 SRSLTE_API int srslte_ue_ul_pusch_encode_rnti_softbuffer(srslte_ue_ul_t *q, uint8_t *data, srslte_uci_data_t uci_data,
                                                          srslte_softbuffer_tx_t *softbuffer, uint16_t rnti,
                                                          cf_t *output_signal);
+/* PUSCH in SRS subframes (36.211 5.3.4, 36.212 5.2.2.6-5.2.2.8).  rule: MI_PUSCH_SRS_OFF (0, the default: always 12
+ * data symbols), MI_PUSCH_SRS_OVERLAP (1) or MI_PUSCH_SRS_ALL_CS (2) of mi_ul.h.  srslte_ue_ul_cfg_grant then decides
+ * with mi_ul_pusch_n_srs, from set_cfg's srs_cfg, the TTI and the final per-slot PRBs (after hopping), whether the
+ * grant's PUSCH leaves the last symbol free; ue_sends_srs = srs_cfg.configured and tti is both a cell-specific and a
+ * UE-specific SRS instant (srslte_refsignal_srs_send_cs / _send_ue).  A shortened grant has grant.nof_symb = 11.
+ * pusch_encode_rnti_softbuffer keeps the rv 0 transmission's symbol count in the softbuffer (n_symb_initial) and uses
+ * it in a retransmission's Q' formulas; when ue_sends_srs it runs the SRS of mi_ue_ul_srs_encode into symbol 13 after
+ * the PUSCH kernels on the instance's stream, so the one call returns PUSCH and SRS in one subframe.  srsUE: set the
+ * rule in init_cell and skip the separate SRS call in subframes that carried a PUSCH.
+ * mi_ue_ul_last_pusch_n_srs: n_srs of the last PUSCH encoded (0 / 1).  Limits: no aperiodic SRS, FDD (no UpPTS),
+ * normal CP, M_sc^PUSCH-initial = the retransmission's M. */
+SRSLTE_API void mi_ue_ul_set_pusch_srs(srslte_ue_ul_t *q, uint32_t rule);
+SRSLTE_API uint32_t mi_ue_ul_last_pusch_n_srs(srslte_ue_ul_t *q);
 /* PUCCH (36.211 5.4, srsue_amd/csrc/pucch.hip): the arguments and return convention of the PUCCH encode call of
  * srsUE's worker (phch_worker.cc:610), under the library's own name.  Format and resource follow 36.213 10.1 (FDD)
  * from uci_data: HARQ-ACK (1 or 2 bits) on n_cce + N_pucch_1 as format 1a / 1b, on n_pucch_sr with a positive
@@ -431,13 +445,14 @@ SRSLTE_API int mi_ue_ul_pucch_encode(srslte_ue_ul_t *q, srslte_uci_data_t uci_da
  * by nof_prb / (15 sqrt(m_srs / 2)) (the PUSCH factor with L_prb = m_srs / 2, the same count of occupied
  * subcarriers; unverified against srsLTE like it); set_cfo applies as for PUSCH.  Whether tti is an SRS instant is
  * not checked: srsUE decides that (phch_worker.cc:529-536).  Limits: FDD, normal CP, one antenna port, no aperiodic
- * SRS; srsUE's worker never sends the SRS together with PUSCH or PUCCH in one subframe (mi_srs_batch_* in mi_ul.h
- * can lay it over a shortened PUCCH).  Returns SRSLTE_ERROR (mi_last_error) when srs_cfg.configured is false or
+ * SRS; srsUE's worker never sends the SRS together with PUCCH in one subframe (mi_srs_batch_* in mi_ul.h can lay it
+ * over a shortened PUCCH); together with PUSCH it goes through the PUSCH encode call (mi_ue_ul_set_pusch_srs).  Returns SRSLTE_ERROR (mi_last_error) when srs_cfg.configured is false or
  * the configuration is rejected (mi_srs_resource). */
 SRSLTE_API int mi_ue_ul_srs_encode(srslte_ue_ul_t *q, uint32_t tti, cf_t *output_signal);
 /* Open-loop UL power control (36.213 5.1; mi_ul_pusch_power, mi_ul_pucch_power, mi_ul_srs_power of mi_ul.h on
  * set_cfg's power_ctrl) with the argument lists of srsUE's worker (phch_worker.cc:568, :622, :652); dBm, capped at
- * P_CMAX = 23.  _pusch_power: of the grant planned by the last srslte_ue_ul_cfg_grant, p0_preamble != 0 marks a
+ * P_CMAX = 23.  _pusch_power: of the grant planned by the last srslte_ue_ul_cfg_grant (N_RE from its n_symb_initial:
+ * the softbuffer's after a pusch_encode of a retransmission, else 12 - n_srs), p0_preamble != 0 marks a
  * grant of the random-access response; _pucch_power: format 0..5 = 1, 1a, 1b, 2, 2a, 2b (q->last_pucch_format);
  * _srs_power: m_srs of set_cfg's srs_cfg (0 when SRS is not configured or rejected).  Limit: no TPC accumulation
  * (f(i) = g(i) = 0; acc_enabled is stored and unused). */

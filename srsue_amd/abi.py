@@ -173,6 +173,9 @@ def lib():
             "mi_ul_batch_stage_ms": (C.c_int, [vp, vp, vp]),
             "mi_ul_batch_profile_reset": (None, [vp]),
             "mi_ul_batch_algo_bytes": (C.c_double, [vp]),
+            "mi_ul_pusch_resource": (C.c_int, [vp, vp]),
+            "mi_ul_pusch_n_srs": (C.c_int, [u32, u32, u32, u32, u32, u32, u32, C.c_int, u32]),
+            "mi_ul_pusch_power_nsymb": (C.c_float, [vp, C.c_float, C.c_float, u32, u32, u32]),
             "mi_pucch_resource": (C.c_int, [vp, vp]),
             "mi_pucch_resource_n": (u32, [vp, u32, vp]),
             "mi_pucch_select": (C.c_int, [u32, C.c_int, u32, C.c_int, u32, u32, u32, u32, vp]),
@@ -920,20 +923,45 @@ class UlCfg(C.Structure):
                                           "group_hopping", "sequence_hopping", "delta_ss", "cyclic_shift", "n_dmrs2",
                                           "ack_len", "ack", "I_offset_ack", "hop", "n_prb1", "cqi_len",
                                           "I_offset_cqi")] + [("cqi", C.c_uint8 * 64)] + \
-        [(n, C.c_uint32) for n in ("ri_len", "ri", "I_offset_ri")]
+        [(n, C.c_uint32) for n in ("ri_len", "ri", "I_offset_ri", "n_srs", "n_symb_initial")]
+
+
+class UlRes(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("n_symb", "G", "q_ack", "q_ri", "q_cqi", "C")] + [("E", C.c_uint32 * 16)]
+
+
+PUSCH_SRS_OFF, PUSCH_SRS_OVERLAP, PUSCH_SRS_ALL_CS = range(3)
 
 
 def ul_cfg(cell_id=1, nof_prb=100, sf_idx=1, rnti=0x46, n_prb=0, L_prb=100, tbs=0, Qm=4, rv=0, gh=0, sh=0, dss=0,
-           cs=0, n2=0, ack_len=0, ack=0, ioff=0, n_prb1=None, cqi=(), cqi_ioff=2, ri_len=0, ri=0, ri_ioff=0):
+           cs=0, n2=0, ack_len=0, ack=0, ioff=0, n_prb1=None, cqi=(), cqi_ioff=2, ri_len=0, ri=0, ri_ioff=0, n_srs=0,
+           n_symb_initial=0):
     """n_prb1: start PRB of slot 1 (frequency hopping), None = no hopping; cqi: CQI bits o_0.. (36.212
-    5.2.2.6.4) with beta_offset index cqi_ioff; ri_len / ri / ri_ioff: RI on PUSCH"""
+    5.2.2.6.4) with beta_offset index cqi_ioff; ri_len / ri / ri_ioff: RI on PUSCH; n_srs = 1: the last symbol is left
+    to the SRS (11 data symbols); n_symb_initial: N_symb^PUSCH-initial of the Q' formulas, 0 = 12 - n_srs"""
     hop, n1 = (0, 0) if n_prb1 is None else (1, n_prb1)
     c = UlCfg(cell_id, nof_prb, sf_idx, rnti, n_prb, L_prb, tbs, Qm, rv, gh, sh, dss, cs, n2, ack_len, ack, ioff,
               hop, n1, len(cqi), cqi_ioff)
     for i, b in enumerate(cqi):
         c.cqi[i] = b
     c.ri_len, c.ri, c.I_offset_ri = ri_len, ri, ri_ioff
+    c.n_srs, c.n_symb_initial = n_srs, n_symb_initial
     return c
+
+
+def ul_pusch_resource(cfg):
+    """mi_ul_pusch_resource: the planned UlRes (n_symb, G, Q' values, C, E[]); raises on a rejected configuration"""
+    r = UlRes()
+    if lib().mi_ul_pusch_resource(C.byref(cfg), C.byref(r)):
+        raise RuntimeError("mi_ul_pusch_resource: " + last_error())
+    return r
+
+
+def ul_pusch_n_srs(nof_prb, srs_subframe_config, srs_bw_cfg, sf_idx, n_prb0, n_prb1, L_prb, ue_sends_srs=0,
+                   rule=PUSCH_SRS_OVERLAP):
+    """mi_ul_pusch_n_srs: 1 if the PUSCH leaves the last symbol to the SRS, 0 if not, -1 for bad arguments"""
+    return lib().mi_ul_pusch_n_srs(nof_prb, srs_subframe_config, srs_bw_cfg, sf_idx, n_prb0, n_prb1, L_prb,
+                                   int(ue_sends_srs), rule)
 
 
 class UlBatch:
@@ -980,8 +1008,8 @@ class UlBatch:
             raise RuntimeError("mi_ul_batch_run: " + last_error())
 
     def symbols(self, i):
-        M = 12 * self.cfgs[i].L_prb
-        out = np.zeros(12 * M, np.uint8)
+        c = self.cfgs[i]
+        out = np.zeros((12 - c.n_srs) * 12 * c.L_prb, np.uint8)   # g, then the Q'_RI cells as zeros
         if lib().mi_ul_batch_symbols(self.h, i, out.ctypes.data):
             raise RuntimeError("mi_ul_batch_symbols: " + last_error())
         return out
@@ -1250,6 +1278,11 @@ def ul_power_cfg(p0_nominal_pusch=-80.0, alpha=0.8, p0_nominal_pucch=-100.0, del
 def ul_pusch_power(cfg, PL, p0_preamble=0.0, L_prb=1, sum_Kr=0):
     """mi_ul_pusch_power (36.213 5.1.1.1), dBm"""
     return lib().mi_ul_pusch_power(C.byref(cfg), PL, p0_preamble, L_prb, sum_Kr)
+
+
+def ul_pusch_power_nsymb(cfg, PL, p0_preamble=0.0, L_prb=1, sum_Kr=0, n_symb_initial=12):
+    """mi_ul_pusch_power_nsymb: mi_ul_pusch_power with N_RE = 12 L_prb n_symb_initial, dBm"""
+    return lib().mi_ul_pusch_power_nsymb(C.byref(cfg), PL, p0_preamble, L_prb, sum_Kr, n_symb_initial)
 
 
 def ul_pucch_power(cfg, PL, format=PUCCH_1A, n_cqi=0, n_harq=0):

@@ -134,4 +134,24 @@ uint32_t mi_srs_resource_n(const mi_srs_cfg_t* c, uint32_t n, mi_srs_res_t* r) {
 
 int mi_srs_resource(const mi_srs_cfg_t* c, mi_srs_res_t* r) { return mi_srs_resource_n(c, 1, r) == 1 ? 0 : -1; }
 
+int srslte_refsignal_srs_send_cs(uint32_t subframe_config, uint32_t sf_idx);   // srslte_util.cpp (srslte/srslte.h)
+
+// 36.211 5.3.4: the PUSCH leaves the last symbol of a subframe in which the UE sends its SRS, and of a cell-specific
+// SRS subframe when its PRBs meet the cell's sounding band (the m_SRS,0 PRBs centred in the carrier, 5.5.3.2)
+int mi_ul_pusch_n_srs(uint32_t nof_prb, uint32_t srs_subframe_config, uint32_t srs_bw_cfg, uint32_t sf_idx, uint32_t n_prb0,
+                      uint32_t n_prb1, uint32_t L_prb, int ue_sends_srs, uint32_t rule) {
+  if (!mi::std_nof_prb(nof_prb) || srs_subframe_config > 14 || srs_bw_cfg > 7 || sf_idx > 9 || L_prb < 1 ||
+      n_prb0 + L_prb > nof_prb || n_prb1 + L_prb > nof_prb || rule > MI_PUSCH_SRS_ALL_CS)
+    return -1;
+  const uint32_t m0 = mi::M_SRS[mi::bw_table(nof_prb)][0][srs_bw_cfg];
+  if (m0 > nof_prb) return -1;
+  if (rule == MI_PUSCH_SRS_OFF) return 0;
+  if (ue_sends_srs) return 1;
+  if (srslte_refsignal_srs_send_cs(srs_subframe_config, sf_idx) != 1) return 0;
+  if (rule == MI_PUSCH_SRS_ALL_CS) return 1;
+  const uint32_t lo = nof_prb / 2 - m0 / 2, hi = lo + m0;   // the band is PRBs lo .. hi - 1
+  auto meets = [&](uint32_t p) { return p < hi && p + L_prb > lo; };
+  return meets(n_prb0) || meets(n_prb1) ? 1 : 0;
+}
+
 }  // extern "C"

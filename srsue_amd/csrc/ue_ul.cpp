@@ -6,8 +6,10 @@
 // A retransmission (rv > 0) re-encodes the TB kept in the HARQ softbuffer: the circular buffer is a
 // deterministic function of the TB, so this equals srsLTE's reuse of its stored coded bits.
 // mi_ue_ul_pucch_encode (PUCCH, pucch.hip) and mi_ue_ul_srs_encode (SRS, srs.hip) share the instance's stream and
-// output staging and nothing else.  mi_ue_ul_pusch_power / _pucch_power / _srs_power are the open-loop power
-// control of ul_power.cpp on set_cfg's parameters.
+// output staging and nothing else.  Under mi_ue_ul_set_pusch_srs cfg_grant shortens the PUSCH of an SRS subframe
+// (mi_ul_pusch_n_srs) and pusch_encode lays the UE's own SRS into the freed symbol before its one fetch.
+// mi_ue_ul_pusch_power / _pucch_power / _srs_power are the open-loop power control of ul_power.cpp on set_cfg's
+// parameters.
 #include <time.h>
 #include <math.h>
 #include <stdlib.h>
@@ -40,6 +42,11 @@ struct mi_ue_ul_ctx {
   mi::SrsEngine srs;
   srslte_refsignal_srs_cfg_t srs_cfg{};
   mi_ul_power_cfg_t power{};
+  // PUSCH in SRS subframes: the rule of mi_ue_ul_set_pusch_srs; whether the planned grant's subframe carries this
+  // UE's SRS (cfg_grant); n_srs of the last PUSCH encoded
+  uint32_t pusch_srs_rule = MI_PUSCH_SRS_OFF;
+  bool ue_sends_srs = false;
+  uint32_t last_n_srs = 0;
   // per-phase host-clock breakdown of pusch_encode (MI_UE_UL_PROF=1: the stream is synchronised at every
   // mark so GPU work is attributed to its phase; printed to stderr when the instance is freed):
   // 0 payload H2D, 1 plan, 2 table upload, 3 kernels, 4 IQ D2H + copy out
@@ -163,6 +170,38 @@ uint32_t rba_bits(uint32_t nof_prb) {
   while ((1u << b) < nof_prb * (nof_prb + 1) / 2) b++;
   return b;
 }
+void srs_cfg_of(const srslte_ue_ul_t* q, uint32_t tti, mi_srs_cfg_t* p) {
+  const srslte_refsignal_srs_cfg_t& s = q->ctx->srs_cfg;
+  *p = mi_srs_cfg_t{};
+  p->cell_id = q->cell.id;
+  p->nof_prb = q->cell.nof_prb;
+  p->tti = tti;
+  p->bw_cfg = s.bw_cfg;
+  p->B = s.B;
+  p->b_hop = s.b_hop;
+  p->n_rrc = s.n_rrc;
+  p->k_tc = s.k_tc;
+  p->n_srs = s.n_srs;
+  p->I_srs = s.I_srs;
+  p->group_hopping = q->dmrs_cfg.group_hopping_en;
+  p->sequence_hopping = q->dmrs_cfg.sequence_hopping_en;
+  p->delta_ss = q->dmrs_cfg.delta_ss;
+}
+
+// plan the SRS of subframe tti and enqueue it on the instance's stream into d_iq: the whole subframe, or
+// (last_symbol_only) symbol 13 alone over the PUSCH written before it
+int srs_enqueue(srslte_ue_ul_t* q, uint32_t tti, bool last_symbol_only) {
+  mi_ue_ul_ctx* c = q->ctx;
+  mi_srs_cfg_t p;
+  srs_cfg_of(q, tti, &p);
+  if (c->srs.plan.build(&p, 1)) return SRSLTE_ERROR;   // every field checked: nothing is launched on an error
+  MiSrsTx& t = c->srs.plan.txs[0];
+  // the PUSCH factor with L_prb = m_srs / 2: the same count of occupied subcarriers
+  if (q->normalize_en) t.scale = (float)q->cell.nof_prb / 15.0f / sqrtf((float)c->srs.plan.res[0].m_srs / 2.0f);
+  if (q->cfo_en) t.cfo = q->current_cfo;
+  c->srs.last_symbol_only = last_symbol_only;
+  return c->srs.upload(c->st) || c->srs.run(nullptr, nullptr, c->d_iq.p, c->st) ? SRSLTE_ERROR : SRSLTE_SUCCESS;
+}
 }  // namespace
 
 extern "C" {
@@ -204,6 +243,11 @@ void srslte_ue_ul_set_cfo_enable(srslte_ue_ul_t* q, bool enabled) {
 void srslte_ue_ul_set_cfo(srslte_ue_ul_t* q, float cur_cfo) {
   if (q) q->current_cfo = cur_cfo;
 }
+
+void mi_ue_ul_set_pusch_srs(srslte_ue_ul_t* q, uint32_t rule) {
+  if (q && q->ctx) q->ctx->pusch_srs_rule = rule <= MI_PUSCH_SRS_ALL_CS ? rule : (uint32_t)MI_PUSCH_SRS_OFF;
+}
+uint32_t mi_ue_ul_last_pusch_n_srs(srslte_ue_ul_t* q) { return q && q->ctx ? q->ctx->last_n_srs : 0; }
 
 void srslte_ue_ul_set_cfg(srslte_ue_ul_t* q, srslte_refsignal_dmrs_pusch_cfg_t* dmrs_cfg,
                           srslte_refsignal_srs_cfg_t* srs_cfg, srslte_pucch_cfg_t* pucch_cfg,
@@ -294,6 +338,22 @@ int srslte_ue_ul_cfg_grant(srslte_ue_ul_t* q, srslte_ra_ul_grant_t* grant, uint3
   c.delta_ss = q->dmrs_cfg.delta_ss;
   c.cyclic_shift = q->dmrs_cfg.cyclic_shift;
   c.n_dmrs2 = grant->ncs_dmrs;
+  // 36.211 5.3.4: the last symbol is left to the SRS under the instance's rule, from the final per-slot PRBs
+  c.n_srs = 0;
+  c.n_symb_initial = 0;   // 12 - n_srs; a retransmission takes the softbuffer's at encode time
+  q->ctx->ue_sends_srs = false;
+  if (q->ctx->pusch_srs_rule != MI_PUSCH_SRS_OFF) {
+    const srslte_refsignal_srs_cfg_t& s = q->ctx->srs_cfg;
+    const bool ue_srs = s.configured && srslte_refsignal_srs_send_cs(s.subframe_config, tti % 10) == 1 &&
+                        srslte_refsignal_srs_send_ue(s.I_srs, tti) == 1;
+    const int n_srs = mi_ul_pusch_n_srs(q->cell.nof_prb, s.subframe_config, s.bw_cfg, tti % 10, c.n_prb,
+                                        c.hop ? c.n_prb1 : c.n_prb, c.L_prb, ue_srs ? 1 : 0, q->ctx->pusch_srs_rule);
+    if (n_srs < 0) { mi::set_error("PUSCH: SRS configuration (subframe_config 0..14, bw_cfg 0..7 within nof_prb)"); return SRSLTE_ERROR; }
+    c.n_srs = (uint32_t)n_srs;
+    q->ctx->ue_sends_srs = ue_srs;
+    q->pusch_cfg.grant.nof_symb = 12 - c.n_srs;
+    q->pusch_cfg.grant.nof_re = (12 - c.n_srs) * 12 * c.L_prb;
+  }
   q->ctx->planned = false;   // the scrambling sequence needs the RNTI: planned at encode time
   return SRSLTE_SUCCESS;
 }
@@ -319,6 +379,8 @@ int srslte_ue_ul_pusch_encode_rnti_softbuffer(srslte_ue_ul_t* q, uint8_t* data, 
   c->cfg.I_offset_ri = q->uci_cfg.I_offset_ri;
   const uint32_t nbytes = c->cfg.tbs / 8;
   if (nbytes > TX_MAX_BYTES) return SRSLTE_ERROR;
+  // N_symb^PUSCH-initial (36.212 5.2.2.6): this subframe's at rv 0, the stored first transmission's afterwards
+  c->cfg.n_symb_initial = c->cfg.rv != 0 && sb && sb->tbs == c->cfg.tbs ? sb->n_symb_initial : 0;
   // the TB: new data from `data`; a retransmission without data re-encodes the softbuffer's copy
   const void* src = nullptr;
   c->prof.start();
@@ -330,6 +392,7 @@ int srslte_ue_ul_pusch_encode_rnti_softbuffer(srslte_ue_ul_t* q, uint8_t* data, 
       if (!mi::hip_ok(hipMemcpyAsync(sb->dev, c->d_pay.p, nbytes, hipMemcpyDeviceToDevice, c->st), "softbuffer"))
         return SRSLTE_ERROR;
       sb->tbs = c->cfg.tbs;
+      sb->n_symb_initial = 12 - c->cfg.n_srs;
     }
     src = c->d_pay.p;
   } else if (sb && sb->dev && sb->tbs == c->cfg.tbs) {
@@ -348,6 +411,9 @@ int srslte_ue_ul_pusch_encode_rnti_softbuffer(srslte_ue_ul_t* q, uint8_t* data, 
   if (c->eng.upload(c->st)) return SRSLTE_ERROR;
   c->prof.mark(2, c->st);
   if (c->eng.run(src, c->d_iq.p, c->st)) return SRSLTE_ERROR;
+  // the UE's own SRS into symbol 13, which the shortened PUSCH above wrote as zeros
+  if (c->ue_sends_srs && c->cfg.n_srs && srs_enqueue(q, q->pusch_cfg.tti, true)) return SRSLTE_ERROR;
+  c->last_n_srs = c->cfg.n_srs;
   c->prof.mark(3, c->st);
   if (c->fetch(n, output_signal, "ul sync")) return SRSLTE_ERROR;
   c->prof.mark(4, c->st);
@@ -404,45 +470,20 @@ int mi_ue_ul_pucch_encode(srslte_ue_ul_t* q, srslte_uci_data_t uci, uint32_t pdc
 // set_cfg's SRS configuration and the DMRS configuration's hopping flags, encoded on the instance's stream by
 // srs.hip, the subframe copied to output_signal.  Whether tti is an SRS instant is the caller's decision
 // (phch_worker.cc:529-536).
-static void srs_cfg_of(const srslte_ue_ul_t* q, uint32_t tti, mi_srs_cfg_t* p) {
-  const srslte_refsignal_srs_cfg_t& s = q->ctx->srs_cfg;
-  *p = mi_srs_cfg_t{};
-  p->cell_id = q->cell.id;
-  p->nof_prb = q->cell.nof_prb;
-  p->tti = tti;
-  p->bw_cfg = s.bw_cfg;
-  p->B = s.B;
-  p->b_hop = s.b_hop;
-  p->n_rrc = s.n_rrc;
-  p->k_tc = s.k_tc;
-  p->n_srs = s.n_srs;
-  p->I_srs = s.I_srs;
-  p->group_hopping = q->dmrs_cfg.group_hopping_en;
-  p->sequence_hopping = q->dmrs_cfg.sequence_hopping_en;
-  p->delta_ss = q->dmrs_cfg.delta_ss;
-}
-
 int mi_ue_ul_srs_encode(srslte_ue_ul_t* q, uint32_t tti, cf_t* output_signal) {
   if (!q || !q->ctx || !output_signal) return SRSLTE_ERROR_INVALID_INPUTS;
-  mi_ue_ul_ctx* c = q->ctx;
-  if (!c->srs_cfg.configured) { mi::set_error("SRS: not configured"); return SRSLTE_ERROR; }
-  mi_srs_cfg_t p;
-  srs_cfg_of(q, tti, &p);
-  if (c->srs.plan.build(&p, 1)) return SRSLTE_ERROR;   // every field checked: nothing is launched on an error
-  MiSrsTx& t = c->srs.plan.txs[0];
-  // the PUSCH factor with L_prb = m_srs / 2: the same count of occupied subcarriers
-  if (q->normalize_en) t.scale = (float)q->cell.nof_prb / 15.0f / sqrtf((float)c->srs.plan.res[0].m_srs / 2.0f);
-  if (q->cfo_en) t.cfo = q->current_cfo;
-  const size_t n = (size_t)15 * mi::symbol_sz(q->cell.nof_prb);
-  if (c->srs.upload(c->st) || c->srs.run(nullptr, nullptr, c->d_iq.p, c->st)) return SRSLTE_ERROR;
-  return c->fetch(n, output_signal, "srs sync");
+  if (!q->ctx->srs_cfg.configured) { mi::set_error("SRS: not configured"); return SRSLTE_ERROR; }
+  if (srs_enqueue(q, tti, false)) return SRSLTE_ERROR;
+  return q->ctx->fetch((size_t)15 * mi::symbol_sz(q->cell.nof_prb), output_signal, "srs sync");
 }
 
 // Open-loop UL power control (36.213 5.1, ul_power.cpp) with srsUE's argument lists (phch_worker.cc:568, :622, :652)
 float mi_ue_ul_pusch_power(srslte_ue_ul_t* q, float PL, float p0_preamble) {
   if (!q || !q->ctx) return 0.0f;
   const srslte_cbsegm_t& s = q->pusch_cfg.cb_segm;   // of the grant planned by srslte_ue_ul_cfg_grant
-  return mi_ul_pusch_power(&q->ctx->power, PL, p0_preamble, q->pusch_cfg.grant.L_prb, s.C1 * s.K1 + s.C2 * s.K2);
+  const mi_ul_cfg_t& g = q->ctx->cfg;
+  return mi_ul_pusch_power_nsymb(&q->ctx->power, PL, p0_preamble, q->pusch_cfg.grant.L_prb, s.C1 * s.K1 + s.C2 * s.K2,
+                                 g.n_symb_initial ? g.n_symb_initial : 12 - g.n_srs);
 }
 float mi_ue_ul_pucch_power(srslte_ue_ul_t* q, float PL, uint32_t format, uint32_t n_cqi, uint32_t n_harq) {
   if (!q || !q->ctx) return 0.0f;

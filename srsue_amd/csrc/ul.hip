@@ -10,7 +10,7 @@
 //                     its parity), trellis termination, rate matching through the per-(K, F) selection
 //                     table, Qm coded bits packed per output symbol;
 //   pusch_mod_kernel  one workgroup per (transmission, slot): channel interleaver read (36.212
-//                     5.2.2.8), scrambling, modulation, M-point transform precoding and the DMRS
+//                     5.2.2.8; 11 columns and a zeroed last symbol in an SRS subframe), scrambling, modulation, M-point transform precoding and the DMRS
 //                     sequence, mapping, N-point SC-FDMA transform with the half-subcarrier shift and
 //                     the cyclic prefix -- mixed-radix Stockham transforms in LDS, twiddles staged once
 //                     per workgroup.
@@ -287,8 +287,12 @@ __global__ __launch_bounds__(UL_THREADS) void pusch_mod_kernel(const uint8_t* __
   // allocation's first subcarrier relative to W/2 (slot 1 may hop: 36.213 8.4)
   const int off = (int)(12 * (slot ? x.n_prb1 : x.n_prb)) - (int)(x.W / 2);
   uint32_t pos = (uint32_t)(symbol_offset((int)N, (int)l0) - cp_len((int)N, (int)(l0 % 7)));   // first sample of l0
+  // shortened for the SRS (36.211 5.3.4): C_mux = 11 interleaver columns, and the subframe's last symbol (the last
+  // pass of the workgroup that owns symbol 13) runs no transform: its samples are written as zeros after the loop.
+  // x.n_srs is the same for the whole workgroup, so every thread takes the same number of passes and barriers
+  const uint32_t nsym = per - (x.n_srs && l0 + per == 14 ? 1u : 0u);
   __syncthreads();
-  for (uint32_t ls = l0 % 7; ls < l0 % 7 + per; ls++) {
+  for (uint32_t ls = l0 % 7; ls < l0 % 7 + nsym; ls++) {
     const uint32_t l = 7 * slot + ls, cp = cp_len((int)N, (int)ls);
     if (ls == 3) {
       // DMRS 36.211 5.5.2.1: r(n) = exp(j alpha n) x_q(n mod N_ZC), x_q(m) = exp(-j pi q m (m+1) / N_ZC); for
@@ -302,7 +306,7 @@ __global__ __launch_bounds__(UL_THREADS) void pusch_mod_kernel(const uint8_t* __
       }
       __syncthreads();
     } else {
-      const uint32_t ld = l - (l > 3 ? 1 : 0) - (l > 10 ? 1 : 0);   // data symbol 0..11
+      const uint32_t ld = l - (l > 3 ? 1 : 0) - (l > 10 ? 1 : 0);   // data symbol 0..11 (0..10 when shortened)
       for (uint32_t m = t; m < M; m += UL_THREADS) {
         // channel interleaver (36.212 5.2.2.8): matrix row m, column ld.  RI symbol i sits in row M - 1 - i / 4
         // of column {1, 10, 7, 4}[i % 4], HARQ-ACK symbol i in row M - 1 - i / 4 of column {2, 9, 8, 3}[i % 4]
@@ -330,7 +334,7 @@ __global__ __launch_bounds__(UL_THREADS) void pusch_mod_kernel(const uint8_t* __
         } else {
           // g index of cell (m, ld): cells of the rows above less their RI cells, plus the free cells left of
           // ld in row m (RI cells of rows >= r: min(Q'_RI, 4 (M - r)); row m's fill {1, 10, 7, 4} in order)
-          uint32_t k = 12 * m + ld;
+          uint32_t k = 12 * m + ld - (x.n_srs ? m : 0u);   // C_mux m + ld, C_mux = 12 - n_srs
           if (x.q_ri) {
             const uint32_t below = min(x.q_ri, 4 * (M - 1 - m)), from = min(x.q_ri, 4 * (M - m)), nrow = from - below;
             const uint32_t left = (nrow > 0 && ld > 1) + (nrow > 3 && ld > 4) + (nrow > 2 && ld > 7) + (nrow > 1 && ld > 10);
@@ -394,6 +398,11 @@ __global__ __launch_bounds__(UL_THREADS) void pusch_mod_kernel(const uint8_t* __
     }
     __syncthreads();
     pos += N + cp;
+  }
+  if (nsym < per) {   // symbol 13 of a shortened transmission: pos is its first sample, N + CP zeros end the subframe
+    float2* dst = iq + x.iq_off + pos;
+    const uint32_t n13 = N + (uint32_t)cp_len((int)N, 6);
+    for (uint32_t i = t; i < n13; i += UL_THREADS) dst[i] = make_float2(0.0f, 0.0f);
   }
 }
 

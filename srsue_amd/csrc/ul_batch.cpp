@@ -41,7 +41,7 @@ int mi_ul_batch_symbols(mi_ul_batch_t* b, uint32_t i, uint8_t* host) {
   if (i >= b->eng.plan.txs.size()) { mi::set_error("transmission index"); return -1; }
   const MiUlTx& t = b->eng.plan.txs[i];
   if (!mi::hip_ok(hipDeviceSynchronize(), "sync")) return -1;
-  const size_t h = 12 * (size_t)t.M - t.q_ri;   // the multiplexed sequence g; the RI cells follow as zeros
+  const size_t h = (12 - t.n_srs) * (size_t)t.M - t.q_ri;   // the multiplexed sequence g; the RI cells follow as zeros
   memset(host + h, 0, t.q_ri);
   return mi::hip_ok(hipMemcpy(host, b->eng.d_syms.as<uint8_t>() + t.sym_off, h, hipMemcpyDeviceToHost),
                     "symbols D2H") ? 0 : -1;

@@ -12,7 +12,7 @@ struct MiUlTx {
   uint32_t N, W;         // FFT size, 12 N_RB^UL
   uint32_t n_prb, M, Qm; // first PRB, M = 12 L_prb subcarriers, bits per symbol
   uint32_t n_prb1;       // first PRB of slot 1 (= n_prb without frequency hopping)
-  uint32_t sym_off;      // byte offset of its 12 M coded symbols (Qm bits each, first bit = MSB)
+  uint32_t sym_off;      // byte offset of its coded symbols (Qm bits each, first bit = MSB; 12 M reserved)
   uint32_t scr_off;      // uint32 offset of its scrambling words (36.211 5.3.1, G bits)
   uint32_t pay_off;      // byte offset of its TB payload
   uint32_t tbs;
@@ -30,6 +30,7 @@ struct MiUlTx {
   uint32_t ri_nblk;      // symbols in the encoded RI block (1 or 3)
   uint32_t ri_sym[3];    // as ack_sym
   uint32_t q_cqi;        // CQI coded symbols Q'_CQI at the head of the multiplexed sequence (uploaded with the plan)
+  uint32_t n_srs;        // 1: symbol 13 carries no PUSCH (SRS subframe): 11 interleaver columns, symbol 13 zeros
 };
 
 // one UL-SCH code block

@@ -170,6 +170,64 @@ static uint32_t uci_block(uint32_t len, uint32_t v, uint32_t Qm, uint32_t* out) 
   return 3;
 }
 
+// One transmission's checks and 36.212 5.2.2.6 arithmetic: every field of c is checked, then the symbol count, the
+// Q' values, G and the code blocks' E.  UlPlan::build and mi_ul_pusch_resource both plan through this.
+int ul_pusch_resource(const mi_ul_cfg_t& c, CbSegm* sg, mi_ul_res_t* r) {
+  if (symbol_sz(c.nof_prb) < 0 || c.nof_prb == 0 || c.sf_idx > 9 || c.L_prb < 1 || c.n_prb + c.L_prb > c.nof_prb || (c.hop && c.n_prb1 + c.L_prb > c.nof_prb) ||
+      (c.Qm != 2 && c.Qm != 4 && c.Qm != 6) || c.tbs == 0 || c.tbs % 8 || c.rv > 3) {
+    set_error("invalid UL configuration (L_prb >= 1, allocation inside the cell, Qm 2/4/6, byte-aligned TBS)");
+    return -1;
+  }
+  const uint32_t M = 12 * c.L_prb;
+  if (!ul_radix_plan(M) || !ul_radix_plan((uint32_t)symbol_sz(c.nof_prb))) {
+    set_error("L_prb must be 2^a 3^b 5^c (36.211 5.3.3)");
+    return -1;
+  }
+  if (c.n_srs > 1 || (c.n_symb_initial != 0 && c.n_symb_initial != 11 && c.n_symb_initial != 12)) {
+    set_error("PUSCH: n_srs 0..1, n_symb_initial 0 (= 12 - n_srs), 11 or 12");
+    return -1;
+  }
+  if (cbsegm(c.tbs, sg)) {
+    set_error("segmentation");
+    return -1;
+  }
+  uint64_t sumK = 0;
+  for (uint32_t k = 0; k < sg->C; k++) sumK += k < sg->Cm ? sg->Km : sg->Kp;
+  // RI and CQI on PUSCH (36.212 5.2.2.6): Q'_RI = min(ceil(O M N_initial beta / sum K_r), 4 M); Q'_CQI =
+  // min(ceil((O + L) M N_initial beta / sum K_r), N M - Q'_RI), L = 8 (CRC) for O > 11; N = 12 - n_srs data
+  // symbols in this subframe, N_initial those of the TB's first transmission (M_sc^PUSCH-initial = M)
+  if (c.ri_len > 2 || (c.ri_len && c.I_offset_ri > 12) || c.cqi_len > 64 ||
+      (c.cqi_len && (c.I_offset_cqi < 2 || c.I_offset_cqi > 15))) {
+    set_error("UCI on PUSCH: RI 0..2 bits (beta index 0..12), CQI 0..64 bits (beta index 2..15)");
+    return -1;
+  }
+  if (c.ack_len > 2) {
+    set_error("HARQ-ACK on PUSCH: 1 or 2 bits");
+    return -1;
+  }
+  const uint32_t N = 12 - c.n_srs, Ni = c.n_symb_initial ? c.n_symb_initial : N;
+  auto qprime = [&](uint64_t bits, uint32_t beta8, uint64_t cap) {
+    const uint64_t q = (bits * M * Ni * beta8 + 8 * sumK - 1) / (8 * sumK);
+    return (uint32_t)(q < cap ? q : cap);
+  };
+  mi_ul_res_t o{};
+  o.n_symb = N;
+  o.q_ri = c.ri_len ? qprime(c.ri_len, BETA8_RI[c.I_offset_ri], 4ull * M) : 0;
+  o.q_cqi = c.cqi_len ? qprime(c.cqi_len + (c.cqi_len > 11 ? 8 : 0), BETA8_CQI[c.I_offset_cqi], (uint64_t)N * M - o.q_ri) : 0;
+  // HARQ-ACK punctures the data (5.2.2.8): it takes no cell out of G
+  o.q_ack = c.ack_len ? qprime(c.ack_len, BETA8_ACK[c.I_offset_ack > 14 ? 14 : c.I_offset_ack], 4ull * M) : 0;
+  if (o.q_cqi + o.q_ri >= N * M) {
+    set_error("PUSCH: the UCI leaves no cell for the UL-SCH data");
+    return -1;
+  }
+  // UL-SCH data bits: the N data symbols' cells less the CQI and RI ones (normal CP)
+  o.G = (N * M - o.q_cqi - o.q_ri) * c.Qm;
+  o.C = sg->C;
+  for (uint32_t k = 0; k < sg->C && k < 16; k++) o.E[k] = rm_E(o.G, sg->C, c.Qm, 1, k);
+  *r = o;
+  return 0;
+}
+
 int UlPlan::build(const mi_ul_cfg_t* cfgs, uint32_t n) {
   txs.clear(); cbs.clear(); kdata.clear(); scr.clear(); tw.clear(); tb_cb0.clear(); cqi_syms.clear(); cqi_off.clear();
   pi_off.clear(); tw_off.clear(); sel_off.clear();
@@ -191,12 +249,10 @@ int UlPlan::build(const mi_ul_cfg_t* cfgs, uint32_t n) {
   };
   for (uint32_t i = 0; i < n; i++) {
     const mi_ul_cfg_t& c = cfgs[i];
+    CbSegm sg;
+    mi_ul_res_t res;
+    if (ul_pusch_resource(c, &sg, &res)) return -1;
     const int N = symbol_sz(c.nof_prb);
-    if (N < 0 || c.nof_prb == 0 || c.sf_idx > 9 || c.L_prb < 1 || c.n_prb + c.L_prb > c.nof_prb || (c.hop && c.n_prb1 + c.L_prb > c.nof_prb) ||
-        (c.Qm != 2 && c.Qm != 4 && c.Qm != 6) || c.tbs == 0 || c.tbs % 8 || c.rv > 3) {
-      set_error("invalid UL configuration (L_prb >= 1, allocation inside the cell, Qm 2/4/6, byte-aligned TBS)");
-      return -1;
-    }
     MiUlTx t{};
     t.N = (uint32_t)N;
     t.W = 12 * c.nof_prb;
@@ -208,10 +264,6 @@ int UlPlan::build(const mi_ul_cfg_t* cfgs, uint32_t n) {
     t.cfo = 0.0f;
     t.fact = ul_radix_plan(t.M);
     t.fact_n = ul_radix_plan(t.N);
-    if (!t.fact || !t.fact_n) {
-      set_error("L_prb must be 2^a 3^b 5^c (36.211 5.3.3)");
-      return -1;
-    }
     for (uint32_t s = 0; s < 2; s++)
       if (ul_dmrs_params(c, 2 * c.sf_idx + s, &t.q[s], &t.nzc, &t.ncs[s])) {
         set_error("DMRS parameters");
@@ -219,26 +271,11 @@ int UlPlan::build(const mi_ul_cfg_t* cfgs, uint32_t n) {
       }
     t.twm_off = twiddles(t.M);
     t.twn_off = twiddles(t.N);
-    CbSegm sg;
-    if (cbsegm(c.tbs, &sg)) {
-      set_error("segmentation");
-      return -1;
-    }
-    uint64_t sumK = 0;
-    for (uint32_t r = 0; r < sg.C; r++) sumK += r < sg.Cm ? sg.Km : sg.Kp;
-    // RI and CQI on PUSCH (36.212 5.2.2.6): Q'_RI = min(ceil(O M 12 beta / sum K_r), 4 M); Q'_CQI =
-    // min(ceil((O + L) M 12 beta / sum K_r), 12 M - Q'_RI), L = 8 (CRC) for O > 11
-    if (c.ri_len > 2 || (c.ri_len && c.I_offset_ri > 12) || c.cqi_len > 64 ||
-        (c.cqi_len && (c.I_offset_cqi < 2 || c.I_offset_cqi > 15))) {
-      set_error("UCI on PUSCH: RI 0..2 bits (beta index 0..12), CQI 0..64 bits (beta index 2..15)");
-      return -1;
-    }
-    auto qprime = [&](uint64_t bits, uint32_t beta8, uint64_t cap) {
-      const uint64_t q = (bits * t.M * 12 * beta8 + 8 * sumK - 1) / (8 * sumK);
-      return (uint32_t)(q < cap ? q : cap);
-    };
-    t.q_ri = c.ri_len ? qprime(c.ri_len, BETA8_RI[c.I_offset_ri], 4ull * t.M) : 0;
-    t.q_cqi = c.cqi_len ? qprime(c.cqi_len + (c.cqi_len > 11 ? 8 : 0), BETA8_CQI[c.I_offset_cqi], 12ull * t.M - t.q_ri) : 0;
+    t.n_srs = c.n_srs;
+    t.q_ri = res.q_ri;
+    t.q_cqi = res.q_cqi;
+    t.q_ack = res.q_ack;
+    const uint32_t nsym = res.n_symb;   // data symbols of this subframe: 12 - n_srs
     cqi_off.push_back((uint32_t)cqi_syms.size());
     if (t.q_cqi) {
       std::vector<uint8_t> qb;
@@ -249,17 +286,16 @@ int UlPlan::build(const mi_ul_cfg_t* cfgs, uint32_t n) {
         cqi_syms.push_back((uint8_t)v);
       }
     }
-    // UL-SCH data bits: the 12 data symbols' cells less the CQI and RI ones (normal CP, no SRS)
-    const uint32_t G = (12 * t.M - t.q_cqi - t.q_ri) * c.Qm;
+    const uint32_t G = res.G;
     t.iq_off = iq_samples;
     iq_samples += 15 * (size_t)N;
     t.pay_off = (uint32_t)payload_bytes;
     payload_bytes += c.tbs / 8;
     t.sym_off = (uint32_t)sym_bytes;
-    sym_bytes += 12 * (size_t)t.M;
+    sym_bytes += 12 * (size_t)t.M;   // the stride stays 12 M; a shortened transmission uses 11 M of it
     t.tbs = c.tbs;
     t.scr_off = (uint32_t)scr.size();
-    const uint32_t n_scr = 12 * t.M * c.Qm;   // 36.211 5.3.1 scrambles every coded bit of the subframe (UCI too)
+    const uint32_t n_scr = nsym * t.M * c.Qm;   // 36.211 5.3.1 scrambles every coded bit of the subframe (UCI too)
     {
       const auto key = std::make_pair((c.rnti << 14) | (c.sf_idx << 9) | c.cell_id, n_scr);
       auto it = scr_cache.find(key);
@@ -281,7 +317,7 @@ int UlPlan::build(const mi_ul_cfg_t* cfgs, uint32_t n) {
       b.F = r == 0 ? sg.F : 0;
       b.C = sg.C;
       b.r = r;
-      b.E = rm_E(G, sg.C, c.Qm, 1, r);
+      b.E = r < 16 ? res.E[r] : rm_E(G, sg.C, c.Qm, 1, r);
       b.byte0 = byte0;
       b.nbytes = (b.K - b.F - (sg.C > 1 ? 24 : 0)) / 8;
       byte0 += b.nbytes;
@@ -321,20 +357,11 @@ int UlPlan::build(const mi_ul_cfg_t* cfgs, uint32_t n) {
       b.r0 = st.r0[c.rv];
       cbs.push_back(b);
     }
-    // HARQ-ACK on PUSCH (36.212 5.2.2.6): Q'_ACK = min(ceil(O M 12 beta / sum K_r), 4 M), encoded block
-    // of Tables 5.2.2.6-1 / -2 (x / y placeholders), inserted by the modulation kernel
-    if (c.ack_len) {
-      if (c.ack_len > 2) {
-        set_error("HARQ-ACK on PUSCH: 1 or 2 bits");
-        return -1;
-      }
-      const uint64_t num = (uint64_t)c.ack_len * t.M * 12 * BETA8_ACK[c.I_offset_ack > 14 ? 14 : c.I_offset_ack];
-      const uint64_t qp = (num + 8 * sumK - 1) / (8 * sumK);
-      t.q_ack = (uint32_t)(qp < 4ull * t.M ? qp : 4ull * t.M);
-      t.ack_nblk = uci_block(c.ack_len, c.ack, c.Qm, t.ack_sym);
-    }
+    // HARQ-ACK on PUSCH (36.212 5.2.2.6): the encoded block of Tables 5.2.2.6-1 / -2 (x / y placeholders),
+    // inserted by the modulation kernel over Q'_ACK symbols
+    if (c.ack_len) t.ack_nblk = uci_block(c.ack_len, c.ack, c.Qm, t.ack_sym);
     if (c.ri_len) t.ri_nblk = uci_block(c.ri_len, c.ri, c.Qm, t.ri_sym);   // Tables 5.2.2.6-3 / -4
-    if (byte0 != c.tbs / 8 + 3 || sym != 12 * t.M - t.q_ri) {
+    if (byte0 != c.tbs / 8 + 3 || sym != nsym * t.M - t.q_ri) {
       set_error("UL planner: segmentation / rate-matching bookkeeping");
       return -1;
     }
@@ -346,6 +373,12 @@ int UlPlan::build(const mi_ul_cfg_t* cfgs, uint32_t n) {
 }
 
 }  // namespace mi
+
+extern "C" int mi_ul_pusch_resource(const mi_ul_cfg_t* c, mi_ul_res_t* r) {
+  if (!c || !r) { mi::set_error("PUSCH: null argument"); return -1; }
+  mi::CbSegm sg;
+  return mi::ul_pusch_resource(*c, &sg, r);
+}
 
 // 36.211 5.3.4, PUSCH hopping type 2 (include/mi_ul.h documents the mapping)
 extern "C" int mi_ul_hop_type2(uint32_t nof_prb, uint32_t n_ho, uint32_t n_sb, int intra, uint32_t cell_id,

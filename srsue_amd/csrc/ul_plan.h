@@ -29,6 +29,10 @@ uint32_t ul_radix_plan(uint32_t n);
 // (32, O) block code repeated; O > 11: CRC8, tail-biting convolutional code, 5.1.4.2 rate matching)
 void ul_cqi_code(const uint8_t* o, uint32_t O, uint32_t Q, std::vector<uint8_t>& q);
 
+// every check and the 36.212 5.2.2.6 arithmetic of one transmission (mi_ul_pusch_resource; UlPlan::build plans
+// through it): 0 with *sg and *r filled, or -1 + set_error with *r untouched
+int ul_pusch_resource(const mi_ul_cfg_t& c, CbSegm* sg, mi_ul_res_t* r);
+
 struct UlPlan {
   std::vector<MiUlTx> txs;
   std::vector<MiUlCb> cbs;

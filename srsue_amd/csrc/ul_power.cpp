@@ -13,14 +13,19 @@ float cap(double p) { return (float)(p < (double)MI_UL_P_CMAX ? p : (double)MI_U
 extern "C" {
 
 float mi_ul_pusch_power(const mi_ul_power_cfg_t* p, float PL, float p0_preamble, uint32_t L_prb, uint32_t sum_Kr) {
-  if (!p || !L_prb) return 0.0f;
+  return mi_ul_pusch_power_nsymb(p, PL, p0_preamble, L_prb, sum_Kr, 12);
+}
+
+float mi_ul_pusch_power_nsymb(const mi_ul_power_cfg_t* p, float PL, float p0_preamble, uint32_t L_prb, uint32_t sum_Kr,
+                              uint32_t n_symb_initial) {
+  if (!p || !L_prb || !n_symb_initial) return 0.0f;
   // a grant of the random-access response: j = 2, P0 = P0_PRE + Delta_PREAMBLE_Msg3, alpha = 1
   const bool msg3 = p0_preamble != 0.0f;
   const double p0 = msg3 ? (double)p0_preamble + p->delta_preamble_msg3 : (double)p->p0_nominal_pusch + p->p0_ue_pusch;
   const double alpha = msg3 ? 1.0 : p->alpha;
   double delta_tf = 0.0;
-  if (p->delta_mcs_based) {   // K_S = 1.25, beta_offset^PUSCH = 1 (data is sent); N_RE = 12 M_sc^PUSCH = 144 L_prb
-    const double bpre = (double)sum_Kr / (144.0 * (double)L_prb);
+  if (p->delta_mcs_based) {   // K_S = 1.25, beta_offset^PUSCH = 1 (data is sent); N_RE = M_sc^PUSCH N_symb^PUSCH-initial
+    const double bpre = (double)sum_Kr / (12.0 * (double)n_symb_initial * (double)L_prb);
     delta_tf = 10.0 * log10(pow(2.0, 1.25 * bpre) - 1.0);
   }
   return cap(10.0 * log10((double)L_prb) + p0 + alpha * PL + delta_tf);
