@@ -15,7 +15,9 @@
  * PARITY STATUS: "parity unpinned" against srsLTE's own arithmetic (no reference test or golden
  * vector exists for this path).  The oracle is pinned instead by 3GPP known-answer
  * tests (CRC, Gold, QPP permutations, TBS spot values, 36.212 tail layout) and by transmit-chain
- * ground truth: decoded TB bits must equal the transmitted ones whenever CRC passes.
+ * ground truth: decoded TB bits must equal the transmitted ones whenever CRC passes, and stage by stage by the
+ * independent float64 numpy restatement tests/pdsch_ref.py (tests/test_pdsch_ref.py), which
+ * restates the [X] conventions too: those stay this project's reading of srsLTE.
  */
 #ifndef LTE_ORACLE_H
 #define LTE_ORACLE_H

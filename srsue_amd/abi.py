@@ -227,6 +227,8 @@ def emu():
         E.emu_set_tdec_i16.argtypes = [C.c_int]
         E.emu_set_tdec_x.restype = None
         E.emu_set_tdec_x.argtypes = [C.c_int]
+        E.emu_keep_softbuffer.restype = None
+        E.emu_keep_softbuffer.argtypes = [C.c_int]
         E.emu_payload_offset.restype = C.c_size_t
         E.emu_payload_offset.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         _emu = E

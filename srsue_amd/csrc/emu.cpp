@@ -116,12 +116,20 @@ static mi::TdecLaneResult emu_win_cb(const MiGroupDesc& g, const MiKTab& kt, con
   return r;
 }
 
+// softbuffer arena kept from one emu_decode_llr call to the next (retransmissions: new_tb = 0 lanes combine with it)
+static int g_keep_sb = 0;
+static std::vector<float> g_sb;
+extern "C" void emu_keep_softbuffer(int on) { g_keep_sb = on; g_sb.clear(); }
+
 extern "C" int emu_decode_llr(const mi_dl_sf_cfg_t* cfgs, uint32_t n, const float* llr_concat, uint32_t max_its,
                               uint8_t* payload, uint32_t* tb_ok, uint32_t* tb_its, uint32_t* cb_its) {
   mi::crc24_fill_tables(crc8, crc8b, 0, 1);
   mi::Plan P;
   if (P.build(cfgs, n, true)) return -1;
-  std::vector<float> e(P.e_floats, 0.f), sb(P.sb_floats, 0.f), scr(P.scratch_floats, 0.f);
+  std::vector<float> e(P.e_floats, 0.f), sb_call, scr(P.scratch_floats, 0.f);
+  // HARQ: the kept softbuffer arena lives across calls while the layout's size stays (a batch's arena across runs)
+  std::vector<float>& sb = g_keep_sb ? g_sb : sb_call;
+  if (sb.size() != P.sb_floats) sb.assign(P.sb_floats, 0.f);
   std::vector<uint8_t> dec(P.dec_bytes, 0), cbb(P.lanes.size() * mi::CB_BYTES_STRIDE, 0);
   std::vector<uint32_t> cits(P.lanes.size(), 0), ccrc(P.lanes.size(), 0), ctbp(P.lanes.size(), 0);
   size_t src = 0;

@@ -38,10 +38,11 @@ void turbo_encode(const uint8_t* c, uint32_t K, uint32_t F, uint8_t* d) {
   std::vector<uint32_t> pi;
   qpp_table(K, pi);
   int s1 = 0, s2 = 0;
+  auto in = [&](uint32_t k) -> int { return k < F ? 0 : (c[k] & 1); };   // 36.212 5.1.3.2.1: filler bits enter as 0
   for (uint32_t k = 0; k < K; k++) {
-    d[3 * k] = c[k];
-    d[3 * k + 1] = (uint8_t)rsc(s1, c[k]);
-    d[3 * k + 2] = (uint8_t)rsc(s2, c[pi[k]]);
+    d[3 * k] = (uint8_t)in(k);
+    d[3 * k + 1] = (uint8_t)rsc(s1, in(k));
+    d[3 * k + 2] = (uint8_t)rsc(s2, in(pi[k]));
   }
   uint8_t t[12];
   for (int j = 0; j < 3; j++) {   // termination: input = feedback so the register fills with 0

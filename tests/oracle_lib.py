@@ -96,6 +96,8 @@ def lib():
             "or_crs_seq": (None, [C.c_uint32, C.c_uint32, C.c_uint32, f32]),
             "or_pdsch_re_list": (C.c_int, [C.POINTER(Cell), C.c_uint32, C.c_uint32, u8, u32]),
             "or_rm_E": (C.c_int, [C.c_uint32] * 5),
+            "or_dft": (None, [P(np.float64, flags="C_CONTIGUOUS"), P(np.float64, flags="C_CONTIGUOUS"), C.c_int,
+                              C.c_int]),
             "or_ncb": (C.c_uint32, [C.c_uint32]),
             "or_tcod": (C.c_int, [u8, C.c_uint32, C.c_uint32, u8]),
             "or_rm_tx": (C.c_int, [u8, C.c_uint32, C.c_uint32, C.c_uint32, u8]),
