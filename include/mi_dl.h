@@ -111,6 +111,25 @@ typedef struct mi_dl_batch mi_dl_batch_t;
 /* Plans a batch (host work + device allocation, once).  max_its: turbo iteration cap
  * (srslte_sch_set_max_noi), early stop on the code-block CRC as srsLTE does. */
 mi_dl_batch_t *mi_dl_batch_create(const mi_dl_sf_cfg_t *cfgs, uint32_t n_sf, uint32_t max_its, uint32_t flags);
+/* Receive diversity: a batch of n_rx = 1 or 2 receive antennas (anything else returns NULL and sets
+ * mi_last_error); mi_dl_batch_create is n_rx = 1.  With two antennas the front end (OFDM, channel estimation) runs
+ * per antenna and the demap stage -- alone or fused into rate de-matching -- combines them per RE by maximum-ratio
+ * combining: TM1 x = sum_a y_a h_a* / (sum_a |h_a|^2 + noise); TM2 the SFBC numerators and |h00|^2 + |h11|^2 summed
+ * over the antennas.  Everything after the LLRs exists once.
+ * Layout (antenna planes): the IQ, MI_DL_BUF_GRID, MI_DL_BUF_CE and MI_DL_BUF_METRICS buffers are n_rx consecutive
+ * copies of the single-antenna buffer.  Antenna a of subframe i lives at mi_dl_batch_offset(b, which, i) +
+ * a * mi_dl_batch_rx_stride(b, which) (the element units of mi_dl_batch_offset; 0 for single-plane buffers), its IQ at
+ * sample mi_dl_batch_iq_offset(b, i) + a * mi_dl_batch_iq_rx_stride(b): a radio's per-channel receive buffers map
+ * onto the planes directly.  mi_dl_batch_iq_samples stays one plane's samples; the d_iq of a run holds n_rx planes;
+ * mi_dl_batch_bytes / _upload / _download / _device_ptr cover all planes.  The strides follow a re-plan.
+ * MI_DL_FLAG_IQ_SC16, MI_DL_FLAG_CE_COMPACT and MI_DL_FLAG_KEEP_LLR work as with one antenna (the LLR stream is the
+ * combined one).  mi_dl_ctrl_* and mi_pbch_* on a two-antenna batch read antenna 0 (plane 0): the control channels
+ * are not combined.  The per-TTI srslte_ue_dl_* API stays single-antenna. */
+mi_dl_batch_t *mi_dl_batch_create_rx(const mi_dl_sf_cfg_t *cfgs, uint32_t n_sf, uint32_t n_rx, uint32_t max_its,
+                                     uint32_t flags);
+uint32_t mi_dl_batch_n_rx(const mi_dl_batch_t *b);
+size_t mi_dl_batch_rx_stride(const mi_dl_batch_t *b, int which);
+size_t mi_dl_batch_iq_rx_stride(const mi_dl_batch_t *b);
 void   mi_dl_batch_destroy(mi_dl_batch_t *b);
 /* IQ layout: subframe i starts at sample (cf32) mi_dl_batch_iq_offset(b, i) */
 size_t mi_dl_batch_iq_offset(const mi_dl_batch_t *b, uint32_t sf);
@@ -200,6 +219,8 @@ int    mi_dl_batch_replan(mi_dl_batch_t *b, mi_dl_plan_t *p, void *stream);     
  * allocates; a deployer sizes workspaces per GPU with it (4 workspaces of 12,500 subframes). */
 size_t mi_dl_batch_device_bytes(mi_dl_batch_t *b);
 size_t mi_dl_plan_device_bytes(const mi_dl_plan_t *p, uint32_t max_its, uint32_t flags);
+/* the same for a batch of n_rx receive antennas (0 and an error string for an n_rx other than 1 or 2) */
+size_t mi_dl_plan_device_bytes_rx(const mi_dl_plan_t *p, uint32_t max_its, uint32_t flags, uint32_t n_rx);
 
 /* ---- raw turbo code-block decoding (the srslte_tdec_* contract; BASELINE configs[0] =
  * srsLTE turbodecoder_test).  n_cb code blocks of size K; decoder input per block = 3(K+4) fp32
@@ -375,6 +396,9 @@ int        mi_acq_mib(mi_acq_t *a, uint32_t cell_id, float cfo, uint32_t max_fra
  * until the slot is submitted again, i.e. for one further submit(). */
 typedef struct mi_dl_pipe mi_dl_pipe_t;
 mi_dl_pipe_t  *mi_dl_pipe_create(const mi_dl_sf_cfg_t *cfgs, uint32_t n_sf, uint32_t max_its, uint32_t flags);
+/* two slots of n_rx-antenna batches (mi_dl_batch_create_rx): submit() copies the n_rx IQ planes of host_iq */
+mi_dl_pipe_t  *mi_dl_pipe_create_rx(const mi_dl_sf_cfg_t *cfgs, uint32_t n_sf, uint32_t n_rx, uint32_t max_its,
+                                    uint32_t flags);
 void           mi_dl_pipe_destroy(mi_dl_pipe_t *p);
 int            mi_dl_pipe_submit(mi_dl_pipe_t *p, const void *host_iq);   /* slot, or -1 */
 int            mi_dl_pipe_wait(mi_dl_pipe_t *p, int slot);

@@ -72,6 +72,12 @@ def lib():
         vp, u32, sz = C.c_void_p, C.c_uint32, C.c_size_t
         sig = {
             "mi_dl_batch_create": (vp, [vp, u32, u32, u32]),
+            "mi_dl_batch_create_rx": (vp, [vp, u32, u32, u32, u32]),
+            "mi_dl_batch_n_rx": (u32, [vp]),
+            "mi_dl_batch_rx_stride": (sz, [vp, C.c_int]),
+            "mi_dl_batch_iq_rx_stride": (sz, [vp]),
+            "mi_dl_plan_device_bytes_rx": (sz, [vp, u32, u32, u32]),
+            "mi_dl_pipe_create_rx": (vp, [vp, u32, u32, u32, u32]),
             "mi_dl_batch_destroy": (None, [vp]),
             "mi_dl_batch_iq_offset": (sz, [vp, u32]),
             "mi_dl_batch_iq_samples": (sz, [vp]),
@@ -208,7 +214,12 @@ def lib():
             "mi_ul_pucch_power": (C.c_float, [vp, C.c_float, u32, u32, u32]),
             "mi_ul_srs_power": (C.c_float, [vp, C.c_float, u32]),
         }
+        # the receive-diversity entry points are absent from a library built before them, which an A/B run selects
+        # with SRSUE_AMD_LIB (tools/ab_libs.sh): such a library binds without them, and calling one raises
+        rx_names = {n for n in sig if n.endswith("_rx") or "_rx_" in n or n == "mi_dl_batch_n_rx"}
         for name, (res, args) in sig.items():
+            if name in rx_names and "SRSUE_AMD_LIB" in os.environ and not hasattr(L, name):
+                continue
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L
@@ -231,6 +242,8 @@ def emu():
         E.emu_keep_softbuffer.argtypes = [C.c_int]
         E.emu_payload_offset.restype = C.c_size_t
         E.emu_payload_offset.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        E.emu_pdsch_llr_rx.restype = C.c_int
+        E.emu_pdsch_llr_rx.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         _emu = E
     return _emu
 
@@ -274,13 +287,18 @@ class Batch:
     """Owns one mi_dl_batch_t (planned once; run() only enqueues kernels)."""
 
     def __init__(self, cfgs, max_its=4, profile=False, tdec_i16=True, iq_sc16=False, sched=None, keep_llr=False,
-                 compact_ce=False, seg_rounds=False):
+                 compact_ce=False, seg_rounds=False, n_rx=1, rx_entry=False):
+        """n_rx: receive antennas (1 or 2); the IQ, grid, ce and metrics buffers then hold n_rx planes (rx_stride).
+        One antenna is created through mi_dl_batch_create unless rx_entry asks for mi_dl_batch_create_rx."""
         self.cfgs = list(cfgs)
         self._arr = cfg_array(self.cfgs)
         flags = (FLAG_PROFILE if profile else 0) | (FLAG_TDEC_I16 if tdec_i16 else FLAG_TDEC_GEN) | \
             (FLAG_IQ_SC16 if iq_sc16 else 0) | SCHED_FLAGS[sched] | (FLAG_KEEP_LLR if keep_llr else 0) | \
             (FLAG_CE_COMPACT if compact_ce else 0) | (FLAG_TDEC_SEG if seg_rounds else 0)
-        self.h = lib().mi_dl_batch_create(C.cast(self._arr, C.c_void_p), len(self.cfgs), max_its, flags)
+        if n_rx == 1 and not rx_entry:
+            self.h = lib().mi_dl_batch_create(C.cast(self._arr, C.c_void_p), len(self.cfgs), max_its, flags)
+        else:
+            self.h = lib().mi_dl_batch_create_rx(C.cast(self._arr, C.c_void_p), len(self.cfgs), n_rx, max_its, flags)
         if not self.h:
             raise RuntimeError("mi_dl_batch_create: " + last_error())
 
@@ -308,6 +326,19 @@ class Batch:
 
     def iq_offset(self, sf):
         return lib().mi_dl_batch_iq_offset(self.h, sf)
+
+    @property
+    def n_rx(self):
+        return lib().mi_dl_batch_n_rx(self.h)
+
+    def rx_stride(self, which):
+        """elements (the units of offset()) between the antenna planes of buffer `which`"""
+        return lib().mi_dl_batch_rx_stride(self.h, which)
+
+    @property
+    def iq_rx_stride(self):
+        """samples between the antenna planes of the IQ buffer"""
+        return lib().mi_dl_batch_iq_rx_stride(self.h)
 
     def run(self, d_iq_ptr, stream_ptr=None):
         rc = lib().mi_dl_batch_run(self.h, C.c_void_p(d_iq_ptr), C.c_void_p(stream_ptr or 0))
@@ -427,12 +458,13 @@ class Plan:
             raise RuntimeError("mi_dl_plan_build: " + last_error())
         return self
 
-    def device_bytes(self, max_its=4, compact_ce=True, keep_llr=False, tdec_i16=True):
-        """HBM a batch of this plan would allocate for its work buffers and softbuffer (mi_dl_plan_device_bytes;
-        host only)."""
+    def device_bytes(self, max_its=4, compact_ce=True, keep_llr=False, tdec_i16=True, n_rx=1):
+        """HBM a batch of this plan with n_rx receive antennas would allocate for its work buffers and softbuffer
+        (mi_dl_plan_device_bytes_rx; host only)."""
         flags = (FLAG_TDEC_I16 if tdec_i16 else FLAG_TDEC_GEN) | (FLAG_CE_COMPACT if compact_ce else 0) | \
             (FLAG_KEEP_LLR if keep_llr else 0)
-        n = lib().mi_dl_plan_device_bytes(self.h, max_its, flags)
+        n = lib().mi_dl_plan_device_bytes(self.h, max_its, flags) if n_rx == 1 else \
+            lib().mi_dl_plan_device_bytes_rx(self.h, max_its, flags, n_rx)
         if not n:
             raise RuntimeError("mi_dl_plan_device_bytes: " + last_error())
         return n
@@ -805,12 +837,15 @@ class HostBuffer:
 class Pipe:
     """Double-buffered host-IQ pipeline (mi_dl_pipe_*): submit() returns a slot without blocking."""
 
-    def __init__(self, cfgs, max_its=4, profile=False, tdec_i16=True, iq_sc16=False):
+    def __init__(self, cfgs, max_its=4, profile=False, tdec_i16=True, iq_sc16=False, n_rx=1, keep_llr=False):
+        """n_rx: receive antennas; submit() then copies the n_rx IQ planes of the host buffer"""
         self.cfgs = list(cfgs)
         self._arr = cfg_array(self.cfgs)
         flags = (FLAG_PROFILE if profile else 0) | (FLAG_TDEC_I16 if tdec_i16 else FLAG_TDEC_GEN) | \
-            (FLAG_IQ_SC16 if iq_sc16 else 0)
-        self.h = lib().mi_dl_pipe_create(C.cast(self._arr, C.c_void_p), len(self.cfgs), max_its, flags)
+            (FLAG_IQ_SC16 if iq_sc16 else 0) | (FLAG_KEEP_LLR if keep_llr else 0)
+        arr = C.cast(self._arr, C.c_void_p)
+        self.h = lib().mi_dl_pipe_create(arr, len(self.cfgs), max_its, flags) if n_rx == 1 else \
+            lib().mi_dl_pipe_create_rx(arr, len(self.cfgs), n_rx, max_its, flags)
         if not self.h:
             raise RuntimeError("mi_dl_pipe_create: " + last_error())
 

@@ -10,12 +10,25 @@ namespace mi { const char* last_error(); }
 
 extern "C" {
 
+static bool n_rx_ok(uint32_t n_rx, const char* who) {
+  if (n_rx == 1 || n_rx == 2) return true;
+  mi::set_error(std::string(who) + ": n_rx must be 1 or 2 receive antennas");
+  return false;
+}
+
 mi_dl_batch_t* mi_dl_batch_create(const mi_dl_sf_cfg_t* cfgs, uint32_t n_sf, uint32_t max_its, uint32_t flags) {
+  return mi_dl_batch_create_rx(cfgs, n_sf, 1, max_its, flags);
+}
+
+mi_dl_batch_t* mi_dl_batch_create_rx(const mi_dl_sf_cfg_t* cfgs, uint32_t n_sf, uint32_t n_rx, uint32_t max_its,
+                                     uint32_t flags) {
   if (!cfgs || !n_sf) { mi::set_error("empty batch"); return nullptr; }
+  if (!n_rx_ok(n_rx, "mi_dl_batch_create_rx")) return nullptr;
   auto* b = new mi_dl_batch();
   b->cfgs.assign(cfgs, cfgs + n_sf);
   b->eng.max_its = max_its ? max_its : 4;
   b->eng.flags = flags;
+  b->eng.n_rx = n_rx;
   if (!mi::hip_ok(hipGetDevice(&b->eng.device), "device") || b->eng.plan.build(cfgs, n_sf, true) || b->eng.upload(nullptr, true) ||
       !mi::hip_ok(hipStreamSynchronize(nullptr), "upload sync")) {
     delete b;
@@ -30,21 +43,32 @@ size_t mi_dl_batch_iq_offset(const mi_dl_batch_t* b, uint32_t sf) {
   return sf < b->eng.plan.sfs.size() ? b->eng.plan.sfs[sf].iq_off : 0;
 }
 size_t mi_dl_batch_iq_samples(const mi_dl_batch_t* b) { return b->eng.plan.iq_samples; }
+uint32_t mi_dl_batch_n_rx(const mi_dl_batch_t* b) { return b->eng.n_rx; }
+size_t mi_dl_batch_iq_rx_stride(const mi_dl_batch_t* b) { return b->eng.plan.iq_samples; }
+size_t mi_dl_batch_rx_stride(const mi_dl_batch_t* b, int which) {
+  const mi::Plan& P = b->eng.plan;
+  switch (which) {
+    case MI_DL_BUF_GRID: return P.grid_elems;
+    case MI_DL_BUF_CE: return P.ce_elems;
+    case MI_DL_BUF_METRICS: return P.sfs.size();   // subframes, like mi_dl_batch_offset: 5 floats each
+    default: return 0;                             // every other buffer has one plane
+  }
+}
 size_t mi_dl_batch_payload_offset(const mi_dl_batch_t* b, uint32_t sf) {
   return sf < b->eng.plan.tbs.size() ? b->eng.plan.tbs[sf].pay_off : 0;
 }
 
 static mi::DevBuf* buf_of(mi_dl_batch_t* b, int which, size_t* bytes) {
   const mi::Plan& P = b->eng.plan;
-  const size_t nsf = P.sfs.size();
+  const size_t nsf = P.sfs.size(), n_rx = b->eng.n_rx;
   switch (which) {
-    case MI_DL_BUF_GRID: *bytes = P.grid_elems * 8; return &b->eng.d_grid;
-    case MI_DL_BUF_CE: *bytes = P.ce_elems * 8; return &b->eng.d_ce;
+    case MI_DL_BUF_GRID: *bytes = n_rx * P.grid_elems * 8; return &b->eng.d_grid;
+    case MI_DL_BUF_CE: *bytes = n_rx * P.ce_elems * 8; return &b->eng.d_ce;
     case MI_DL_BUF_LLR: *bytes = P.e_floats * 4; return b->eng.ensure_llr() ? &b->eng.d_e : nullptr;
     case MI_DL_BUF_PAYLOAD: *bytes = P.payload_bytes; return &b->eng.d_payload;
     case MI_DL_BUF_TB_CRC: *bytes = nsf * 4; return &b->eng.d_tbok;
     case MI_DL_BUF_TB_ITS: *bytes = nsf * 4; return &b->eng.d_tbits;
-    case MI_DL_BUF_METRICS: *bytes = nsf * 5 * 4; return &b->eng.d_metrics;
+    case MI_DL_BUF_METRICS: *bytes = n_rx * nsf * 5 * 4; return &b->eng.d_metrics;
     case MI_DL_BUF_CB_ITS: *bytes = P.lanes.size() * 4; return &b->eng.d_cbits;
     case MI_DL_BUF_CB_CRC: *bytes = P.lanes.size() * 4; return &b->eng.d_cbcrc;
     case MI_DL_BUF_SOFTBUFFER: *bytes = P.sb_floats * 4; return &b->eng.d_sb;
@@ -115,9 +139,16 @@ int mi_dl_batch_stage_ms(mi_dl_batch_t* b, float* ms, uint32_t* nruns) { return 
 void mi_dl_batch_profile_reset(mi_dl_batch_t* b) { b->eng.profile_reset(); }
 
 double mi_dl_batch_algo_bytes(const mi_dl_batch_t* b, int which_stage) {
-  if (which_stage < 0) return b->eng.plan.bytes_compulsory;
+  // every antenna beyond the first adds its IQ, its OFDM and channel-estimation stage and the demap's reads of its
+  // grid and estimates; the LLRs, the softbuffer and everything after them exist once
+  const mi::Plan& P = b->eng.plan;
+  const double extra = (double)(b->eng.n_rx - 1);
+  if (which_stage < 0) return P.bytes_compulsory + extra * P.iq_bytes;
   if (which_stage >= MI_DL_NSTAGES) return 0;
-  return b->eng.plan.stage_bytes[which_stage];
+  const double s = P.stage_bytes[which_stage];
+  if (which_stage == MI_DL_STAGE_OFDM || which_stage == MI_DL_STAGE_CHEST) return s + extra * s;
+  if (which_stage == MI_DL_STAGE_DEMAP) return s + extra * P.demap_in_bytes;
+  return s;
 }
 
 uint32_t mi_dl_batch_n_codeblocks(const mi_dl_batch_t* b) { return b->eng.plan.n_cb; }
@@ -146,11 +177,17 @@ size_t mi_dl_batch_device_bytes(mi_dl_batch_t* b) {
 }
 
 size_t mi_dl_plan_device_bytes(const mi_dl_plan_t* p, uint32_t max_its, uint32_t flags) {
+  return mi_dl_plan_device_bytes_rx(p, max_its, flags, 1);
+}
+
+size_t mi_dl_plan_device_bytes_rx(const mi_dl_plan_t* p, uint32_t max_its, uint32_t flags, uint32_t n_rx) {
   if (!p || !p->built) { mi::set_error("mi_dl_plan_device_bytes: no built plan"); return 0; }
+  if (!n_rx_ok(n_rx, "mi_dl_plan_device_bytes_rx")) return 0;
   mi::Engine e;   // host only: the sizes of the buffers a batch of this plan would allocate
   static_cast<mi::PlanData&>(e.plan) = p->plan;
   e.max_its = max_its ? max_its : 4;
   e.flags = flags;
+  e.n_rx = n_rx;
   return e.work_bytes(true, (flags & MI_DL_FLAG_KEEP_LLR) != 0);
 }
 
@@ -291,14 +328,20 @@ struct mi_dl_pipe {
 extern "C" {
 
 mi_dl_pipe_t* mi_dl_pipe_create(const mi_dl_sf_cfg_t* cfgs, uint32_t n_sf, uint32_t max_its, uint32_t flags) {
+  return mi_dl_pipe_create_rx(cfgs, n_sf, 1, max_its, flags);
+}
+
+mi_dl_pipe_t* mi_dl_pipe_create_rx(const mi_dl_sf_cfg_t* cfgs, uint32_t n_sf, uint32_t n_rx, uint32_t max_its,
+                                   uint32_t flags) {
+  if (!n_rx_ok(n_rx, "mi_dl_pipe_create_rx")) return nullptr;
   auto* p = new mi_dl_pipe();
   bool ok = mi::hip_ok(hipStreamCreateWithFlags(&p->copy, hipStreamNonBlocking), "stream") &&
             mi::hip_ok(hipStreamCreateWithFlags(&p->comp, hipStreamNonBlocking), "stream");
   for (int s = 0; ok && s < 2; s++) {
-    p->slot[s] = mi_dl_batch_create(cfgs, n_sf, max_its, flags);
+    p->slot[s] = mi_dl_batch_create_rx(cfgs, n_sf, n_rx, max_its, flags);
     ok = p->slot[s] != nullptr;
     if (ok) {
-      p->iq_bytes = mi_dl_batch_iq_samples(p->slot[s]) * ((flags & MI_DL_FLAG_IQ_SC16) ? 4 : 8);
+      p->iq_bytes = n_rx * mi_dl_batch_iq_samples(p->slot[s]) * ((flags & MI_DL_FLAG_IQ_SC16) ? 4 : 8);   // all planes
       ok = p->iq[s].ensure(p->iq_bytes) &&
            mi::hip_ok(hipEventCreateWithFlags(&p->copied[s], hipEventDisableTiming), "event") &&
            mi::hip_ok(hipEventCreateWithFlags(&p->decoded[s], hipEventDisableTiming), "event");

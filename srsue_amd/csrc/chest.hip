@@ -28,7 +28,7 @@ __global__ __launch_bounds__(256) void chest_kernel(const float2* __restrict__ g
                                                    const MiSfDesc* __restrict__ sfs,
                                                    const MiCellDesc* __restrict__ cells,
                                                    const float2* __restrict__ crs, float* __restrict__ metrics,
-                                                   uint32_t compact) {
+                                                   uint32_t compact, size_t grid_rx, size_t ce_rx) {
   constexpr int PL[4] = {0, 4, 7, 11};
   constexpr float W1 = 0.1f, W0 = 0.8f;
   __shared__ float2 hp[4][2 * NRB_MAX];
@@ -37,7 +37,8 @@ __global__ __launch_bounds__(256) void chest_kernel(const float2* __restrict__ g
   const MiSfDesc d = sfs[blockIdx.x];
   const MiCellDesc c = cells[d.cell];
   const int W = (int)c.W, NP = 2 * (int)c.nof_prb;
-  const float2* g = grid + d.grid_off;
+  // blockIdx.y: the receive antenna (its grid / estimate planes grid_rx / ce_rx elements apart)
+  const float2* g = grid + d.grid_off + blockIdx.y * grid_rx;
   float rsrp = 0.f, noise = 0.f, rssi = 0.f;
   // every loop runs over (uniform row, thread-strided column): no integer division by runtime sizes
   const int tid = (int)threadIdx.x;
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) void chest_kernel(const float2* __restrict__ g
     // frequency interpolation of the 4 pilot symbols at subcarrier k (kept in registers), then the
     // time interpolation / extrapolation of all 14 symbols at k: coalesced rows of ce[port][l][k]
     // compact (MI_DL_FLAG_CE_COMPACT): the 4 frequency-interpolated pilot rows [port][4][W] only
-    float2* cp = ce + d.ce_off + (size_t)p * (compact ? 4 : NSYMB) * W;
+    float2* cp = ce + d.ce_off + blockIdx.y * ce_rx + (size_t)p * (compact ? 4 : NSYMB) * W;
     for (int k = tid; k < W; k += 256) {
       float2 hk[4];
 #pragma unroll
@@ -117,17 +118,17 @@ __global__ __launch_bounds__(256) void chest_kernel(const float2* __restrict__ g
   rssi = block_sum(rssi, red);
   if (threadIdx.x == 0) {
     const float rs = rsrp / (float)(4 * NP), no = noise / (float)(4 * NP * c.nof_ports), ri = rssi / 4.0f;
-    float* m = metrics + (size_t)blockIdx.x * 5;
+    float* m = metrics + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 5;   // [antenna][subframe][5]
     m[0] = rs; m[1] = ri; m[2] = ri > 0.f ? (float)c.nof_prb * rs / ri : 0.f;
     m[3] = no; m[4] = no > 0.f ? rs / no : 0.f;
   }
 }
 
 void launch_chest(const float2* grid, float2* ce, const MiSfDesc* sfs, const MiCellDesc* cells, const float2* crs,
-                  float* metrics, uint32_t n_sf, hipStream_t st, bool compact) {
+                  float* metrics, uint32_t n_sf, const RxPlanes& rx, hipStream_t st, bool compact) {
   if (!n_sf) return;
-  hipLaunchKernelGGL(chest_kernel, dim3(n_sf), dim3(256), 0, st, grid, ce, sfs, cells, crs, metrics,
-                     (uint32_t)compact);
+  hipLaunchKernelGGL(chest_kernel, dim3(n_sf, rx.n), dim3(256), 0, st, grid, ce, sfs, cells, crs, metrics,
+                     (uint32_t)compact, rx.grid, rx.ce);
 }
 
 }  // namespace mi

@@ -29,29 +29,62 @@ __device__ __forceinline__ void demap_store(float2 x, const uint32_t* __restrict
   for (int b = 0; b < QM; b += 2) o[b / 2] = make_float2(l[b], l[b + 1]);
 }
 
-template <int QM>
+// antenna a's grid at g + a g_rx, its estimates at c0 / c1 + a c_rx (the batch's antenna planes)
+template <int QM, int NRX>
 __device__ __forceinline__ void demap_unit(const MiPdschDesc& pd, uint32_t u, const float2* __restrict__ g,
                                            const float2* __restrict__ c0, const float2* __restrict__ c1,
                                            const uint32_t* __restrict__ re, const uint32_t* __restrict__ scr,
-                                           float* __restrict__ e, float noise) {
-  if (pd.tm != 2) {
+                                           float* __restrict__ e, float noise, size_t g_rx, size_t c_rx) {
+  if constexpr (NRX == 1) {   // one antenna: the loads as direct arguments (demap_body.h demap_llr)
+    if (pd.tm != 2) {
+      const uint32_t r = re[u];
+      demap_store<QM>(eq_single(g[r], c0[r], noise), scr, u * QM, e);
+    } else {
+      const uint32_t ra = re[2 * u], rb = re[2 * u + 1];
+      float2 x0, x1;
+      eq_sfbc(g[ra], g[rb], c0[ra], c0[rb], c1[ra], c1[rb], &x0, &x1);
+      demap_store<QM>(x0, scr, 2 * u * QM, e);
+      demap_store<QM>(x1, scr, (2 * u + 1) * QM, e);
+    }
+  } else if (pd.tm != 2) {
     const uint32_t r = re[u];
-    demap_store<QM>(eq_single(g[r], c0[r], noise), scr, u * QM, e);
+    EqIn d;
+    d.r0 = g[r];
+    d.h00 = c0[r];
+    EqAcc<false> acc = eq_terms<false>(d);
+#pragma unroll
+    for (int a = 1; a < NRX; a++) {
+      d.r0 = g[a * g_rx + r];
+      d.h00 = c0[a * c_rx + r];
+      eq_add<false>(acc, d);
+    }
+    float2 x;
+    eq_finish<false>(acc, noise, &x, nullptr);
+    demap_store<QM>(x, scr, u * QM, e);
   } else {
     const uint32_t ra = re[2 * u], rb = re[2 * u + 1];
+    EqAcc<true> acc = eq_terms<true>(EqIn{g[ra], g[rb], c0[ra], c0[rb], c1[ra], c1[rb]});
+#pragma unroll
+    for (int a = 1; a < NRX; a++) {
+      const float2 *ga = g + a * g_rx, *p0 = c0 + a * c_rx, *p1 = c1 + a * c_rx;
+      eq_add<true>(acc, EqIn{ga[ra], ga[rb], p0[ra], p0[rb], p1[ra], p1[rb]});
+    }
     float2 x0, x1;
-    eq_sfbc(g[ra], g[rb], c0[ra], c0[rb], c1[ra], c1[rb], &x0, &x1);
+    eq_finish<true>(acc, noise, &x0, &x1);
     demap_store<QM>(x0, scr, 2 * u * QM, e);
     demap_store<QM>(x1, scr, (2 * u + 1) * QM, e);
   }
 }
 
+// NRX receive antennas combined per unit (demap_body.h eq_terms / eq_add / eq_finish); the antenna planes' strides are launch arguments
+template <int NRX>
 __global__ __launch_bounds__(256) void demap_kernel(const float2* __restrict__ grid, const float2* __restrict__ ce,
                                                    float* __restrict__ e, const MiSfDesc* __restrict__ sfs,
                                                    const MiPdschDesc* __restrict__ pds,
                                                    const MiCellDesc* __restrict__ cells,
                                                    const uint32_t* __restrict__ re_tab,
-                                                   const uint32_t* __restrict__ scr_tab, float noise) {
+                                                   const uint32_t* __restrict__ scr_tab, float noise, size_t g_rx,
+                                                   size_t c_rx) {
   const MiSfDesc d = sfs[blockIdx.y];
   const MiPdschDesc pd = pds[d.pdsch];
   const uint32_t units = pd.tm == 2 ? pd.nre / 2 : pd.nre;
@@ -65,18 +98,23 @@ __global__ __launch_bounds__(256) void demap_kernel(const float2* __restrict__ g
   const uint32_t* scr = scr_tab + pd.scr_off;
   float* out = e + d.e_off;
   switch (pd.Qm) {
-    case 2: demap_unit<2>(pd, u, g, c0, c1, re, scr, out, noise); break;
-    case 4: demap_unit<4>(pd, u, g, c0, c1, re, scr, out, noise); break;
-    default: demap_unit<6>(pd, u, g, c0, c1, re, scr, out, noise); break;
+    case 2: demap_unit<2, NRX>(pd, u, g, c0, c1, re, scr, out, noise, g_rx, c_rx); break;
+    case 4: demap_unit<4, NRX>(pd, u, g, c0, c1, re, scr, out, noise, g_rx, c_rx); break;
+    default: demap_unit<6, NRX>(pd, u, g, c0, c1, re, scr, out, noise, g_rx, c_rx); break;
   }
 }
 
 void launch_demap(const float2* grid, const float2* ce, float* e, const MiSfDesc* sfs, const MiPdschDesc* pd,
                   const MiCellDesc* cells, const uint32_t* re_tab, const uint32_t* scr, uint32_t n_sf,
-                  uint32_t max_units, float noise, hipStream_t st) {
+                  uint32_t max_units, float noise, const RxPlanes& rx, hipStream_t st) {
   if (!n_sf || !max_units) return;
   dim3 g((max_units + 255) / 256, n_sf);
-  hipLaunchKernelGGL(demap_kernel, g, dim3(256), 0, st, grid, ce, e, sfs, pd, cells, re_tab, scr, noise);
+  if (rx.n == 2)
+    hipLaunchKernelGGL(demap_kernel<2>, g, dim3(256), 0, st, grid, ce, e, sfs, pd, cells, re_tab, scr, noise, rx.grid,
+                       rx.ce);
+  else
+    hipLaunchKernelGGL(demap_kernel<1>, g, dim3(256), 0, st, grid, ce, e, sfs, pd, cells, re_tab, scr, noise, rx.grid,
+                       rx.ce);
 }
 
 }  // namespace mi

@@ -4,6 +4,9 @@
 // srslte_scrambling_f, inside srslte_pdsch_decode_rnti, /root/reference/ue/src/phy/phch_worker.cc:347).
 #pragma once
 #include "dl_common.h"
+#if defined(MI_EMU)
+#define __forceinline__ inline   // host emulation build (emu.cpp emu_pdsch_llr_rx): the same arithmetic with g++
+#endif
 
 namespace mi {
 
@@ -17,13 +20,13 @@ namespace mi {
 #else
 #define MI_FP_EXACT
 #endif
-// TM1 MMSE: y h* / (|h|^2 + noise)
+// TM1 MMSE, one antenna: y h* / (|h|^2 + noise)
 __device__ __forceinline__ float2 eq_single(float2 y, float2 h, float noise) {
   MI_FP_EXACT
   const float den = h.x * h.x + h.y * h.y + noise;
   return make_float2((y.x * h.x + y.y * h.y) / den, (y.y * h.x - y.x * h.y) / den);
 }
-// TM2 SFBC (Alamouti) pair: symbols x0 (k = 0) and x1 (k = 1) of REs ra / rb
+// TM2 SFBC (Alamouti) pair, one antenna: symbols x0 (k = 0) and x1 (k = 1) of REs ra / rb
 __device__ __forceinline__ void eq_sfbc(float2 r0, float2 r1, float2 h00, float2 h01, float2 h10, float2 h11,
                                        float2* x0, float2* x1) {
   MI_FP_EXACT
@@ -34,6 +37,80 @@ __device__ __forceinline__ void eq_sfbc(float2 r0, float2 r1, float2 h00, float2
                     sc * ((h00.x * r0.y - h00.y * r0.x) + (h11.y * r1.x - h11.x * r1.y)));
   *x1 = make_float2(sc * (-(h10.x * r0.x + h10.y * r0.y) + (h01.x * r1.x + h01.y * r1.y)),
                     sc * (-(h10.y * r0.x - h10.x * r0.y) + (h01.x * r1.y - h01.y * r1.x)));
+}
+// Receive diversity: maximum-ratio combining over the receive antennas, for every path that forms LLRs.
+//   TM1 MMSE: x = sum_a y_a h_a* / (sum_a |h_a|^2 + noise)
+//   TM2 SFBC pair: hh = sum_a (|h00_a|^2 + |h11_a|^2),  x0 = sqrt2 sum_a (h00_a* r0_a + h11_a r1_a*) / hh,
+//                  x1 = sqrt2 sum_a (-h10_a r0_a* + h01_a* r1_a) / hh     (hh <= 0 -> 1e-9 after the sum)
+// An antenna's terms (eq_terms) are formed exactly as eq_single / eq_sfbc form them, added in antenna order
+// (eq_add), the regulariser last (eq_finish): with one antenna the result is eq_single's / eq_sfbc's floats, and the
+// one-antenna instantiations call those two directly (the same instructions as before receive diversity).  The
+// caller loads one antenna's inputs at a time, so no two antennas' six values are live at once:
+//   EqAcc<TM2> s = eq_terms<TM2>(in_0);  for a = 1 .. n_rx - 1: eq_add<TM2>(s, in_a);  eq_finish<TM2>(s, noise, &x0, &x1);
+// The inputs of one demap unit at one antenna: TM1 an RE (r0, h00); TM2 an SFBC RE pair (ra, rb) with the estimates
+// h[port][RE] = h00 h01 / h10 h11
+struct EqIn {
+  float2 r0, r1, h00, h01, h10, h11;
+};
+// the running sums (named scalars, no arrays: they must stay in registers)
+template <bool TM2>
+struct EqAcc;
+template <>
+struct EqAcc<false> {
+  float nx, ny, den;   // numerator re / im, sum |h|^2
+};
+template <>
+struct EqAcc<true> {
+  float hh, ax, ay, bx, by;   // sum (|h00|^2 + |h11|^2), x0 re / im and x1 re / im before the scaling
+};
+template <bool TM2>
+__device__ __forceinline__ EqAcc<TM2> eq_terms(const EqIn& d) {
+  MI_FP_EXACT
+  EqAcc<TM2> t;
+  if constexpr (!TM2) {
+    const float2 y = d.r0, h = d.h00;
+    t.nx = y.x * h.x + y.y * h.y;
+    t.ny = y.y * h.x - y.x * h.y;
+    t.den = h.x * h.x + h.y * h.y;
+  } else {
+    const float2 r0 = d.r0, r1 = d.r1, h00 = d.h00, h01 = d.h01, h10 = d.h10, h11 = d.h11;
+    t.hh = h00.x * h00.x + h00.y * h00.y + h11.x * h11.x + h11.y * h11.y;
+    t.ax = (h00.x * r0.x + h00.y * r0.y) + (h11.x * r1.x + h11.y * r1.y);
+    t.ay = (h00.x * r0.y - h00.y * r0.x) + (h11.y * r1.x - h11.x * r1.y);
+    t.bx = -(h10.x * r0.x + h10.y * r0.y) + (h01.x * r1.x + h01.y * r1.y);
+    t.by = -(h10.y * r0.x - h10.x * r0.y) + (h01.x * r1.y - h01.y * r1.x);
+  }
+  return t;
+}
+template <bool TM2>
+__device__ __forceinline__ void eq_add(EqAcc<TM2>& s, const EqIn& d) {
+  MI_FP_EXACT
+  const EqAcc<TM2> t = eq_terms<TM2>(d);
+  if constexpr (!TM2) {
+    s.nx = s.nx + t.nx;
+    s.ny = s.ny + t.ny;
+    s.den = s.den + t.den;
+  } else {
+    s.hh = s.hh + t.hh;
+    s.ax = s.ax + t.ax;
+    s.ay = s.ay + t.ay;
+    s.bx = s.bx + t.bx;
+    s.by = s.by + t.by;
+  }
+}
+template <bool TM2>
+__device__ __forceinline__ void eq_finish(const EqAcc<TM2>& s, float noise, float2* x0, float2* x1 /* TM2 only */) {
+  MI_FP_EXACT
+  if constexpr (!TM2) {
+    const float den = s.den + noise;
+    *x0 = make_float2(s.nx / den, s.ny / den);
+  } else {
+    float hh = s.hh;
+    if (hh <= 0.f) hh = 1e-9f;
+    const float sc = 1.41421356237309504880f / hh;
+    *x0 = make_float2(sc * s.ax, sc * s.ay);
+    *x1 = make_float2(sc * s.bx, sc * s.by);
+  }
 }
 
 template <int QM>
@@ -98,22 +175,50 @@ __device__ __forceinline__ float demap_bit(float x, uint32_t j) {
 }
 
 // one LLR of a PDSCH subframe: bit `gi` of the subframe's LLR stream (after descrambling), computed
-// from the grid and channel estimates exactly as demap_kernel computes it (TM1: one RE per Qm bits; TM2:
-// one SFBC RE pair per 2 Qm bits)
-template <int QM>
+// from the grids and channel estimates of the NRX antennas (antenna a's at g + a g_rx, c0 + a c_rx, c1 + a c_rx)
+// exactly as demap_kernel computes it (TM1: one RE per Qm bits; TM2: one SFBC RE pair per 2 Qm bits)
+template <int QM, int NRX>
 __device__ __forceinline__ float demap_llr(const MiPdschDesc& pd, uint32_t gi, const float2* __restrict__ g,
                                            const float2* __restrict__ c0, const float2* __restrict__ c1,
                                            const uint32_t* __restrict__ re, const uint32_t* __restrict__ scr,
-                                           float noise) {
+                                           float noise, size_t g_rx, size_t c_rx) {
   const uint32_t s = gi / QM, b = gi - s * QM;   // data symbol, bit within it
   float2 x;
-  if (pd.tm != 2) {
+  if constexpr (NRX == 1) {
+    // one antenna: the loads as direct arguments, as before receive diversity (through a loader the compiler schedules
+    // this path differently inside the rate de-matching combine loop, which runs at its register budget: rm.hip)
+    if (pd.tm != 2) {
+      const uint32_t r = re[s];
+      x = eq_single(g[r], c0[r], noise);
+    } else {
+      const uint32_t u = s >> 1, ra = re[2 * u], rb = re[2 * u + 1];
+      float2 x0, x1;
+      eq_sfbc(g[ra], g[rb], c0[ra], c0[rb], c1[ra], c1[rb], &x0, &x1);
+      x = (s & 1) == 0 ? x0 : x1;
+    }
+  } else if (pd.tm != 2) {
     const uint32_t r = re[s];
-    x = eq_single(g[r], c0[r], noise);
+    EqIn d;
+    d.r0 = g[r];
+    d.h00 = c0[r];
+    EqAcc<false> acc = eq_terms<false>(d);
+#pragma unroll
+    for (int a = 1; a < NRX; a++) {
+      d.r0 = g[a * g_rx + r];
+      d.h00 = c0[a * c_rx + r];
+      eq_add<false>(acc, d);
+    }
+    eq_finish<false>(acc, noise, &x, nullptr);
   } else {
     const uint32_t u = s >> 1, ra = re[2 * u], rb = re[2 * u + 1];
     float2 x0, x1;
-    eq_sfbc(g[ra], g[rb], c0[ra], c0[rb], c1[ra], c1[rb], &x0, &x1);
+    EqAcc<true> acc = eq_terms<true>(EqIn{g[ra], g[rb], c0[ra], c0[rb], c1[ra], c1[rb]});
+#pragma unroll
+    for (int a = 1; a < NRX; a++) {
+      const float2 *ga = g + a * g_rx, *p0 = c0 + a * c_rx, *p1 = c1 + a * c_rx;
+      eq_add<true>(acc, EqIn{ga[ra], ga[rb], p0[ra], p0[rb], p1[ra], p1[rb]});
+    }
+    eq_finish<true>(acc, noise, &x0, &x1);
     x = (s & 1) == 0 ? x0 : x1;
   }
   const float v = demap_bit<QM>((b & 1) ? x.y : x.x, b >> 1);   // I: even bits, Q: odd bits

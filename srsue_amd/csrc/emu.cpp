@@ -12,6 +12,7 @@
 
 #include <vector>
 
+#include "demap_body.h"
 #include "kernels_consts.h"
 #include "plan.h"
 #include "rm_body.h"
@@ -344,6 +345,33 @@ extern "C" size_t emu_payload_offset(const mi_dl_sf_cfg_t* cfgs, uint32_t n, uin
   mi::Plan P;
   if (P.build(cfgs, n, true)) return 0;
   return P.tbs[sf].pay_off;
+}
+
+// The G LLRs of one PDSCH subframe from n_rx antennas' grids ([n_rx][14][W] float2) and channel estimates
+// ([n_rx][ports][14][W] float2): demap_body.h demap_llr -- the kernels' equalisation with antenna combining, demapper
+// and descrambling -- over the planner's RE list and scrambling words, bit by bit.  out: G floats.  Returns G, -1 on a
+// bad configuration or antenna count.
+template <int NRX>
+static void emu_llr_run(const MiPdschDesc& pd, const float2* g, const float2* c0, size_t W, const uint32_t* re,
+                        const uint32_t* scr, float noise, size_t g_rx, size_t c_rx, float* out) {
+  const float2* c1 = c0 + (size_t)mi::NSYMB * W;
+  for (uint32_t gi = 0; gi < pd.G; gi++)
+    out[gi] = pd.Qm == 2   ? mi::demap_llr<2, NRX>(pd, gi, g, c0, c1, re, scr, noise, g_rx, c_rx)
+              : pd.Qm == 4 ? mi::demap_llr<4, NRX>(pd, gi, g, c0, c1, re, scr, noise, g_rx, c_rx)
+                           : mi::demap_llr<6, NRX>(pd, gi, g, c0, c1, re, scr, noise, g_rx, c_rx);
+}
+extern "C" int emu_pdsch_llr_rx(const mi_dl_sf_cfg_t* cfg, uint32_t n_rx, const float* grids, const float* ces,
+                                float noise, float* out) {
+  mi::Plan P;
+  if (n_rx < 1 || n_rx > 2 || P.build(cfg, 1, true)) return -1;
+  const MiPdschDesc& pd = P.pds[P.sfs[0].pdsch];
+  const size_t W = 12 * (size_t)cfg->nof_prb, g_rx = (size_t)mi::NSYMB * W, c_rx = g_rx * cfg->nof_ports;
+  const float2* g = reinterpret_cast<const float2*>(grids);
+  const float2* c0 = reinterpret_cast<const float2*>(ces);
+  const uint32_t *re = &P.re_tab[pd.re_off], *scr = &P.scr_tab[pd.scr_off];
+  if (n_rx == 2) emu_llr_run<2>(pd, g, c0, W, re, scr, noise, g_rx, c_rx, out);
+  else emu_llr_run<1>(pd, g, c0, W, re, scr, noise, g_rx, c_rx, out);
+  return (int)pd.G;
 }
 
 // The packed decoder's trellis start (tdec_p2_body.h header, p2.h tadd_a): the LLRs of steps 0..2 taken from the start

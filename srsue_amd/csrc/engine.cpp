@@ -198,7 +198,9 @@ int Engine::ensure_work(hipStream_t st, bool alloc_sb) {
 std::vector<std::pair<DevBuf*, size_t>> Engine::work_set() {
   const Plan& P = plan;
   const size_t nsf = std::max<size_t>(P.sfs.size(), 1);
-  std::vector<std::pair<DevBuf*, size_t>> w{{&d_grid, P.grid_elems * 8}, {&d_ce, P.ce_elems * 8}, {&d_metrics, nsf * 5 * 4}};
+  // n_rx antenna planes of the grid, the channel estimates and the metrics (kernels.h RxPlanes)
+  std::vector<std::pair<DevBuf*, size_t>> w{{&d_grid, n_rx * P.grid_elems * 8}, {&d_ce, n_rx * P.ce_elems * 8},
+                                            {&d_metrics, n_rx * nsf * 5 * 4}};
   if (P.has_pdsch || P.cb_n) {
     w.insert(w.end(), {{&d_wm, P.groups.size() * WM_STRIDE * 4}, {&d_scratch, P.scratch_floats * 4},
                        {&d_dec, P.dec_bytes}, {&d_cbbytes, (size_t)P.lanes.size() * CB_BYTES_STRIDE},
@@ -321,6 +323,7 @@ int Engine::run(const void* d_iq, hipStream_t st, uint32_t mask, float* sb_overr
     cur = *back;
   };
   const uint32_t nsf = (uint32_t)P.sfs.size();
+  const RxPlanes rx{n_rx, P.iq_samples, P.grid_elems, P.ce_elems};   // the strides follow the current plan
   // compact channel estimates (MI_DL_FLAG_CE_COMPACT): only when this run both writes and consumes them
   // (channel estimation and the fused demap in one run), nothing else reads the full estimates, and no
   // code block repeats LLRs (the single-LLR repetition path reads full estimates)
@@ -339,13 +342,13 @@ int Engine::run(const void* d_iq, hipStream_t st, uint32_t mask, float* sb_overr
       const int N = P.fft_lists[i].first;
       launch_ofdm_rx(N, d_iq, (flags & MI_DL_FLAG_IQ_SC16) != 0, d_grid.as<float2>(), d_sfs.as<MiSfDesc>(),
                      d_fftlist.as<uint32_t>() + P.fft_list_off[i], (uint32_t)P.fft_lists[i].second.size(),
-                     d_tw.as<float2>() + tw_off[N], P.fft_W[i], st);
+                     d_tw.as<float2>() + tw_off[N], P.fft_W[i], rx, st);
     }
   }
   mark(1);
   if (mask & (1u << MI_DL_STAGE_CHEST))
     launch_chest(d_grid.as<float2>(), d_ce.as<float2>(), d_sfs.as<MiSfDesc>(), d_cells.as<MiCellDesc>(),
-                 d_crs.as<float2>(), d_metrics.as<float>(), nsf, st, compact);
+                 d_crs.as<float2>(), d_metrics.as<float>(), nsf, rx, st, compact);
   if (mask & (1u << MI_DL_STAGE_CHEST)) ce_compact = compact;
   mark(2);
   if (P.has_pdsch) {
@@ -357,7 +360,7 @@ int Engine::run(const void* d_iq, hipStream_t st, uint32_t mask, float* sb_overr
     if ((mask & (1u << MI_DL_STAGE_DEMAP)) && !fuse)
       launch_demap(d_grid.as<float2>(), d_ce.as<float2>(), d_e.as<float>(), d_sfs.as<MiSfDesc>(),
                    d_pds.as<MiPdschDesc>(), d_cells.as<MiCellDesc>(), d_re.as<uint32_t>(), d_scr.as<uint32_t>(), nsf,
-                   P.max_units, noise, st);
+                   P.max_units, noise, rx, st);
     mark(3);
     // the direct groups' row maps (Plan::rm_direct) before the combine kernel stages their chunks -- only in a
     // run that rate de-matches (a run without RM must leave the softbuffer, maps included, untouched)
@@ -369,7 +372,7 @@ int Engine::run(const void* d_iq, hipStream_t st, uint32_t mask, float* sb_overr
                       d_scr.as<uint32_t>(), noise, sb, d_groups.as<MiGroupDesc>(), d_lanes.as<MiLaneDesc>(),
                       d_ktabs.as<MiKTab>(), d_kdata.as<uint32_t>(), (uint32_t)P.groups.size(), P.max_ncb, P.unit_kind,
                       rm_items(),
-                      rm_recs(), P.rm_busy, P.rm_dbusy, (uint32_t)P.rm_items.size(), compact, st);
+                      rm_recs(), P.rm_busy, P.rm_dbusy, (uint32_t)P.rm_items.size(), compact, rx, st);
     else if (mask & (1u << MI_DL_STAGE_RM))
       launch_rm_combine(d_e.as<float>(), sb, d_groups.as<MiGroupDesc>(), d_lanes.as<MiLaneDesc>(),
                         d_ktabs.as<MiKTab>(), d_kdata.as<uint32_t>(), (uint32_t)P.groups.size(), P.max_ncb,

@@ -33,6 +33,9 @@ struct DevBuf {
 struct Engine {
   Plan plan;
   uint32_t max_its = 4, early_stop = 1, flags = 0;
+  // receive antennas (1 or 2): the IQ, grid, channel-estimate and metrics buffers hold n_rx planes of the plan's
+  // single-antenna layout (kernels.h RxPlanes); the planner does not know of them
+  uint32_t n_rx = 1;
   // Schedule overrides for A/B runs and equivalence tests, read from the environment ONCE, when the engine (a batch
   // or a per-TTI instance) is created -- never on the run path.  Every choice they force is exact: results are
   // identical either way.  -1 / 0 = automatic.

@@ -8,17 +8,26 @@
 
 namespace mi {
 
-// OFDM RX (srslte_ofdm_rx_sf): one workgroup per subframe, 14 FFTs of size N
+// Receive antennas of a batch (receive diversity): the IQ, grid, channel-estimate and metrics buffers hold n
+// consecutive planes, each laid out as the single-antenna buffer; antenna a of a subframe lives at the subframe's
+// offset + a x the plane stride (IQ samples, float2 grid / estimate elements; metrics: 5 floats per (antenna,
+// subframe)).  Uniform over a launch: kernel arguments, no descriptor carries them.
+struct RxPlanes {
+  uint32_t n = 1;
+  size_t iq = 0, grid = 0, ce = 0;
+};
+// OFDM RX (srslte_ofdm_rx_sf): one workgroup per (subframe, antenna), 14 FFTs of size N
 void launch_ofdm_rx(int N, const void* iq, bool sc16, float2* grid, const MiSfDesc* sfs, const uint32_t* list,
-                    uint32_t n, const float2* tw, uint32_t W, hipStream_t st);
-// channel estimation (srslte_chest_dl_estimate): one workgroup per subframe, all ports
+                    uint32_t n, const float2* tw, uint32_t W, const RxPlanes& rx, hipStream_t st);
+// channel estimation (srslte_chest_dl_estimate): one workgroup per (subframe, antenna), all ports
 void launch_chest(const float2* grid, float2* ce, const MiSfDesc* sfs, const MiCellDesc* cells,
-                  const float2* crs, float* metrics, uint32_t n_sf, hipStream_t st,
+                  const float2* crs, float* metrics, uint32_t n_sf, const RxPlanes& rx, hipStream_t st,
                   bool compact = false /* MI_DL_FLAG_CE_COMPACT: only the 4 pilot rows per port */);
-// equalise + soft demap + descramble (srslte_predecoding_* / demod_soft / scrambling_f)
+// equalise (combining the antennas) + soft demap + descramble (srslte_predecoding_* / demod_soft / scrambling_f)
 void launch_demap(const float2* grid, const float2* ce, float* e, const MiSfDesc* sfs,
                   const MiPdschDesc* pd, const MiCellDesc* cells, const uint32_t* re_tab,
-                  const uint32_t* scr, uint32_t n_sf, uint32_t max_units, float noise, hipStream_t st);
+                  const uint32_t* scr, uint32_t n_sf, uint32_t max_units, float noise, const RxPlanes& rx,
+                  hipStream_t st);
 // rate de-matching + HARQ combining into the group-interleaved softbuffer (srslte_rm_turbo_rx)
 void launch_rm_combine(const float* e, float* sb, const MiGroupDesc* groups, const MiLaneDesc* lanes,
                        const MiKTab* ktabs, const uint32_t* ktab_data, uint32_t n_groups,
@@ -33,7 +42,7 @@ void launch_rm_fused(const float2* grid, const float2* ce, const MiLaneSrc* lane
                      const uint32_t* items /* Plan::rm_items, NULL = every chunk */,
                      const uint4* recs /* Plan::rm_recs: the busy items' folded records */, uint32_t n_busy,
                      uint32_t n_dbusy /* Plan::rm_dbusy: the leading direct-group items */, uint32_t n_items,
-                     bool compact_ce, hipStream_t st);
+                     bool compact_ce, const RxPlanes& rx, hipStream_t st);
 // row maps and zero rows of Plan::rm_direct's groups (rm.hip rm_direct_map_kernel), before the combine launch
 void launch_rm_direct_maps(float* sb, const uint32_t* ktab_data, const MiRmDirect* dgs, uint32_t ndg, hipStream_t st);
 // ---- turbo decoder (srslte_tdec_*) ----

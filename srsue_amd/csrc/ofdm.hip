@@ -196,14 +196,16 @@ template <int N, typename IQ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFDM_WAVES))) void ofdm_rx_kernel(const IQ* __restrict__ iq, float2* __restrict__ grid,
                                                       const MiSfDesc* __restrict__ sfs,
                                                       const uint32_t* __restrict__ list,
-                                                      const float2* __restrict__ twg, uint32_t W, int per) {
+                                                      const float2* __restrict__ twg, uint32_t W, int per,
+                                                      size_t iq_rx, size_t grid_rx) {
   __shared__ float2 buf[N + (N >> OFDM_PAD_SH)];
   __shared__ float2 tw[N / 2];   // half-wave table (tw_at)
   const MiSfDesc d = sfs[list[blockIdx.x]];
   for (int t = threadIdx.x; t < N / 2; t += 256) tw[t] = twg[t];
   __syncthreads();
-  const IQ* src_sf = iq + d.iq_off;
-  float2* dst = grid + d.grid_off;
+  // blockIdx.z: the receive antenna, its IQ and grid planes iq_rx samples / grid_rx elements apart
+  const IQ* src_sf = iq + d.iq_off + blockIdx.z * iq_rx;
+  float2* dst = grid + d.grid_off + blockIdx.z * grid_rx;
   const int l0 = (int)blockIdx.y * per;
   FirstIn<N> cur, nxt;
   first_load<N, IQ>(src_sf + symbol_offset(N, l0), nxt);
@@ -219,25 +221,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OFDM_WAVES)
 
 template <typename IQ>
 static void launch_ofdm_rx_t(int N, const IQ* iq, float2* grid, const MiSfDesc* sfs, const uint32_t* list, uint32_t n,
-                             const float2* tw, uint32_t W, hipStream_t st) {
+                             const float2* tw, uint32_t W, const RxPlanes& rx, hipStream_t st) {
   const int per = n >= 256 ? NSYMB : 1;   // small batches: a workgroup per symbol (latency)
-  dim3 g(n, NSYMB / per), b(256);
+  dim3 g(n, NSYMB / per, rx.n), b(256);
   switch (N) {
-    case 2048: hipLaunchKernelGGL((ofdm_rx_kernel<2048, IQ>), g, b, 0, st, iq, grid, sfs, list, tw, W, per); break;
-    case 1536: hipLaunchKernelGGL((ofdm_rx_kernel<1536, IQ>), g, b, 0, st, iq, grid, sfs, list, tw, W, per); break;
-    case 1024: hipLaunchKernelGGL((ofdm_rx_kernel<1024, IQ>), g, b, 0, st, iq, grid, sfs, list, tw, W, per); break;
-    case 512: hipLaunchKernelGGL((ofdm_rx_kernel<512, IQ>), g, b, 0, st, iq, grid, sfs, list, tw, W, per); break;
-    case 256: hipLaunchKernelGGL((ofdm_rx_kernel<256, IQ>), g, b, 0, st, iq, grid, sfs, list, tw, W, per); break;
-    case 128: hipLaunchKernelGGL((ofdm_rx_kernel<128, IQ>), g, b, 0, st, iq, grid, sfs, list, tw, W, per); break;
+    case 2048: hipLaunchKernelGGL((ofdm_rx_kernel<2048, IQ>), g, b, 0, st, iq, grid, sfs, list, tw, W, per, rx.iq, rx.grid); break;
+    case 1536: hipLaunchKernelGGL((ofdm_rx_kernel<1536, IQ>), g, b, 0, st, iq, grid, sfs, list, tw, W, per, rx.iq, rx.grid); break;
+    case 1024: hipLaunchKernelGGL((ofdm_rx_kernel<1024, IQ>), g, b, 0, st, iq, grid, sfs, list, tw, W, per, rx.iq, rx.grid); break;
+    case 512: hipLaunchKernelGGL((ofdm_rx_kernel<512, IQ>), g, b, 0, st, iq, grid, sfs, list, tw, W, per, rx.iq, rx.grid); break;
+    case 256: hipLaunchKernelGGL((ofdm_rx_kernel<256, IQ>), g, b, 0, st, iq, grid, sfs, list, tw, W, per, rx.iq, rx.grid); break;
+    case 128: hipLaunchKernelGGL((ofdm_rx_kernel<128, IQ>), g, b, 0, st, iq, grid, sfs, list, tw, W, per, rx.iq, rx.grid); break;
     default: break;
   }
 }
 
 void launch_ofdm_rx(int N, const void* iq, bool sc16, float2* grid, const MiSfDesc* sfs, const uint32_t* list,
-                    uint32_t n, const float2* tw, uint32_t W, hipStream_t st) {
+                    uint32_t n, const float2* tw, uint32_t W, const RxPlanes& rx, hipStream_t st) {
   if (n == 0) return;
-  if (sc16) launch_ofdm_rx_t(N, static_cast<const short2*>(iq), grid, sfs, list, n, tw, W, st);
-  else launch_ofdm_rx_t(N, static_cast<const float2*>(iq), grid, sfs, list, n, tw, W, st);
+  if (sc16) launch_ofdm_rx_t(N, static_cast<const short2*>(iq), grid, sfs, list, n, tw, W, rx, st);
+  else launch_ofdm_rx_t(N, static_cast<const float2*>(iq), grid, sfs, list, n, tw, W, rx, st);
 }
 
 }  // namespace mi

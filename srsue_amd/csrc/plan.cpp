@@ -69,6 +69,7 @@ int Plan::build(const mi_dl_sf_cfg_t* cfgs, uint32_t n, bool with_pdsch) {
   max_units = max_ncb = n_cb = 0;
   bytes_compulsory = 0;
   for (double& b : stage_bytes) b = 0;
+  iq_bytes = demap_in_bytes = 0;
   sfs.reserve(n);
   tbs.reserve(n);
 
@@ -130,6 +131,7 @@ int Plan::build(const mi_dl_sf_cfg_t* cfgs, uint32_t n, bool with_pdsch) {
     stage_bytes[MI_DL_STAGE_OFDM] += (double)sf_len(N) * 8 + (double)NSYMB * W * 8;
     stage_bytes[MI_DL_STAGE_CHEST] += (double)NSYMB * W * 8 * c.nof_ports + 4.0 * W * 8;
     bytes_compulsory += (double)sf_len(N) * 8;
+    iq_bytes += (double)sf_len(N) * 8;
 
     if (with_pdsch) {
       if (c.tm == 2 && c.nof_ports != 2) { set_error("TM2 needs 2 ports"); return -1; }
@@ -210,6 +212,7 @@ int Plan::build(const mi_dl_sf_cfg_t* cfgs, uint32_t n, bool with_pdsch) {
         eo += E;
       }
       stage_bytes[MI_DL_STAGE_DEMAP] += (double)pd.nre * 8 * (1 + c.nof_ports) + (double)pd.G * 4;
+      demap_in_bytes += (double)pd.nre * 8 * (1 + c.nof_ports);
       bytes_compulsory += (double)c.tbs / 8;
     }
     sfs.push_back(sd);
@@ -591,6 +594,7 @@ int Plan::build_codeblocks(uint32_t K, uint32_t ncb_req, bool crc24a) {
   bytes_compulsory = 0;
   for (double& b : stage_bytes) b = 0;
 
+  iq_bytes = demap_in_bytes = 0;
   has_pdsch = false;
   cb_K = K;
   cb_n = ncb_req;

@@ -62,6 +62,9 @@ struct PlanData {
   // algorithmic byte counts
   double bytes_compulsory = 0;
   double stage_bytes[MI_DL_NSTAGES] = {0};
+  // the parts of the above that every further receive antenna of a batch adds once more (mi_dl_batch_algo_bytes):
+  // the IQ of bytes_compulsory, and the demap stage's grid and estimate reads
+  double iq_bytes = 0, demap_in_bytes = 0;
   uint32_t cb_K = 0, cb_n = 0;
 };
 

@@ -27,6 +27,12 @@ namespace mi {
 // mix on one stream (profiles/r3/ab_rm_split/ab_g8*): general chunks 977 us with 4-wavefront groups (122 VGPRs, 4 waves
 // per SIMD), 918 us with 8 at 6 waves per SIMD, 1,121 us at 8 (45 VGPRs spilled)
 constexpr int RM_GENERAL_NW = 8, RM_GENERAL_WPE = 6, RM_DIRECT_WPE = 8;
+// two receive antennas (NRX = 2): the staging accumulates a second antenna's values per unit and the repetition path a
+// second set of loads; the waves per SIMD at which those instantiations hold everything in registers
+constexpr int RM_GENERAL_WPE_RX2 = 4, RM_DIRECT_WPE_RX2 = 6;
+constexpr int rm_wpe(bool dir, int nw, int nrx) {
+  return dir ? (nrx > 1 ? RM_DIRECT_WPE_RX2 : RM_DIRECT_WPE) : nw == 8 ? (nrx > 1 ? RM_GENERAL_WPE_RX2 : RM_GENERAL_WPE) : 1;
+}
 
 // workgroup shape: RM_NW wavefronts per chunk, each owning RM_CHUNK / RM_NW = 32 consecutive positions
 // in the combine and 64 / RM_NW code-block rows (2 row-segments each) in the staging
@@ -44,6 +50,8 @@ struct RmFuse {
   const uint32_t* scr_tab;
   float noise;
   uint32_t compact;          // MI_DL_FLAG_CE_COMPACT: ce holds the 4 pilot rows [port][4][W] per subframe
+  size_t grid_rx, ce_rx;     // receive diversity: antenna a's grid / estimate plane at + a grid_rx / a ce_rx (kernels.h
+                             // RxPlanes); the antenna count is the kernel's NRX
 };
 
 // channel estimate of port plane cp at RE index ra (= l W + k): full estimates are read; compact ones are
@@ -64,7 +72,7 @@ struct UnitIdx {
   uint32_t s0, s1;   // the scrambling words holding the unit's first and last bit
 };
 struct UnitIn {
-  float2 r0, r1, h00, h01, h10, h11;   // TM1: r0, h00
+  EqIn q;   // one antenna's grid / estimate values (TM1: r0, h00)
   uint32_t s0, s1;
 };
 template <int QM, bool TM2>
@@ -80,30 +88,29 @@ __device__ __forceinline__ UnitIdx fused_idx(const RmFuse& f, const MiLaneSrc& s
   x.s1 = scr[(bit0 + U - 1) >> 5];
   return x;
 }
+// antenna a's values of the unit (a = 0 for a single-antenna batch)
 template <bool TM2>
-__device__ __forceinline__ UnitIn fused_data(const RmFuse& f, const MiLaneSrc& src, const UnitIdx& x) {
-  const float2* g = f.grid + src.goff;
-  const float2* c0 = f.ce + src.coff;
+__device__ __forceinline__ UnitIn fused_data(const RmFuse& f, const MiLaneSrc& src, const UnitIdx& x, int a = 0) {
+  const float2* g = f.grid + src.goff + a * f.grid_rx;
+  const float2* c0 = f.ce + src.coff + a * f.ce_rx;
   UnitIn d;
-  d.r0 = g[x.ra];
-  d.h00 = ce_at(f, src, c0, x.ra);
+  d.q.r0 = g[x.ra];
+  d.q.h00 = ce_at(f, src, c0, x.ra);
   if constexpr (TM2) {
     const float2* c1 = c0 + (f.compact ? 4 * (src.c1 / NSYMB) : src.c1);
-    d.r1 = g[x.rb];
-    d.h01 = ce_at(f, src, c0, x.rb);
-    d.h10 = ce_at(f, src, c1, x.ra);
-    d.h11 = ce_at(f, src, c1, x.rb);
+    d.q.r1 = g[x.rb];
+    d.q.h01 = ce_at(f, src, c0, x.rb);
+    d.q.h10 = ce_at(f, src, c1, x.ra);
+    d.q.h11 = ce_at(f, src, c1, x.rb);
   }
   d.s0 = x.s0;
   d.s1 = x.s1;
   return d;
 }
-// the U = Qm (TM1) or 2 Qm (TM2) descrambled LLRs of unit u, in LLR order
+// the U = Qm (TM1) or 2 Qm (TM2) descrambled LLRs of unit u, in LLR order, from its equalised symbol(s) x and the
+// scrambling words s0 / s1 of its first and last bit
 template <int QM, bool TM2>
-__device__ __forceinline__ void fused_llrs(const RmFuse& f, const UnitIn& d, uint32_t u, float* out) {
-  float2 x[2];
-  if constexpr (!TM2) x[0] = eq_single(d.r0, d.h00, f.noise);
-  else eq_sfbc(d.r0, d.r1, d.h00, d.h01, d.h10, d.h11, &x[0], &x[1]);
+__device__ __forceinline__ void fused_llrs(const float2* x, uint32_t s0, uint32_t s1, uint32_t u, float* out) {
   constexpr int NS = TM2 ? 2 : 1, U = QM * NS;
   float l[U];
 #pragma unroll
@@ -115,17 +122,17 @@ __device__ __forceinline__ void fused_llrs(const RmFuse& f, const UnitIn& d, uin
 #pragma unroll
   for (int b = 0; b < U; b++) {
     const uint32_t i = bit0 + b;
-    const uint32_t word = (i >> 5) == w0 ? d.s0 : d.s1;
+    const uint32_t word = (i >> 5) == w0 ? s0 : s1;
     out[b] = ((word >> (i & 31)) & 1u) ? -l[b] : l[b];
   }
 }
 // ... into the tile positions of [ga, gb)
 template <int QM, bool TM2>
-__device__ __forceinline__ void fused_compute(const RmFuse& f, const UnitIn& d, uint32_t u, uint32_t ga, uint32_t gb,
-                                              uint32_t ta, float* tile) {
+__device__ __forceinline__ void fused_store(const float2* x, uint32_t s0, uint32_t s1, uint32_t u, uint32_t ga,
+                                            uint32_t gb, uint32_t ta, float* tile) {
   constexpr int U = QM * (TM2 ? 2 : 1);
   float v[U];
-  fused_llrs<QM, TM2>(f, d, u, v);
+  fused_llrs<QM, TM2>(x, s0, s1, u, v);
   const uint32_t bit0 = u * U;
 #pragma unroll
   for (int b = 0; b < U; b++) {
@@ -133,26 +140,49 @@ __device__ __forceinline__ void fused_compute(const RmFuse& f, const UnitIn& d, 
     if (i >= ga && i < gb) tile[ta + (i - ga)] = v[b];
   }
 }
+// a single-antenna unit from its loaded values (the software pipeline's last stage)
 template <int QM, bool TM2>
+__device__ __forceinline__ void fused_compute(const RmFuse& f, const UnitIn& d, uint32_t u, uint32_t ga, uint32_t gb,
+                                              uint32_t ta, float* tile) {
+  float2 x[2];
+  if constexpr (!TM2) x[0] = eq_single(d.q.r0, d.q.h00, f.noise);
+  else eq_sfbc(d.q.r0, d.q.r1, d.q.h00, d.q.h01, d.q.h10, d.q.h11, &x[0], &x[1]);
+  fused_store<QM, TM2>(x, d.s0, d.s1, u, ga, gb, ta, tile);
+}
+// a unit of NRX antennas: each antenna's values are loaded and accumulated in turn (demap_body.h), so the registers
+// hold one antenna's six values at a time
+template <int QM, bool TM2, int NRX>
 __device__ __forceinline__ void fused_unit(const RmFuse& f, const MiLaneSrc& src, uint32_t u, uint32_t ga, uint32_t gb,
                                            uint32_t ta, float* tile) {
-  fused_compute<QM, TM2>(f, fused_data<TM2>(f, src, fused_idx<QM, TM2>(f, src, u)), u, ga, gb, ta, tile);
+  const UnitIdx i = fused_idx<QM, TM2>(f, src, u);
+  if constexpr (NRX == 1) {
+    fused_compute<QM, TM2>(f, fused_data<TM2>(f, src, i), u, ga, gb, ta, tile);
+  } else {
+    EqAcc<TM2> acc = eq_terms<TM2>(fused_data<TM2>(f, src, i, 0).q);
+#pragma unroll
+    for (int a = 1; a < NRX; a++) eq_add<TM2>(acc, fused_data<TM2>(f, src, i, a).q);
+    float2 x[2];
+    eq_finish<TM2>(acc, f.noise, &x[0], &x[1]);
+    fused_store<QM, TM2>(x, i.s0, i.s1, u, ga, gb, ta, tile);
+  }
 }
 
+template <int NRX>
 __device__ __forceinline__ void fused_unit_any(const RmFuse& f, const MiLaneSrc& src, uint32_t u, uint32_t ga,
                                                uint32_t gb, uint32_t ta, float* tile) {
   switch (src.qm + 8 * src.tm2) {
-    case 2: fused_unit<2, false>(f, src, u, ga, gb, ta, tile); break;
-    case 4: fused_unit<4, false>(f, src, u, ga, gb, ta, tile); break;
-    case 6: fused_unit<6, false>(f, src, u, ga, gb, ta, tile); break;
-    case 10: fused_unit<2, true>(f, src, u, ga, gb, ta, tile); break;
-    case 12: fused_unit<4, true>(f, src, u, ga, gb, ta, tile); break;
-    default: fused_unit<6, true>(f, src, u, ga, gb, ta, tile); break;
+    case 2: fused_unit<2, false, NRX>(f, src, u, ga, gb, ta, tile); break;
+    case 4: fused_unit<4, false, NRX>(f, src, u, ga, gb, ta, tile); break;
+    case 6: fused_unit<6, false, NRX>(f, src, u, ga, gb, ta, tile); break;
+    case 10: fused_unit<2, true, NRX>(f, src, u, ga, gb, ta, tile); break;
+    case 12: fused_unit<4, true, NRX>(f, src, u, ga, gb, ta, tile); break;
+    default: fused_unit<6, true, NRX>(f, src, u, ga, gb, ta, tile); break;
   }
 }
 
 // LLR gi of a lane's subframe, alone (repetition beyond N_v, low code rates only): the single-bit
 // form of the same arithmetic (demap_body.h demap_llr)
+template <int NRX>
 __device__ __forceinline__ float fused_llr(const RmFuse& f, const MiLaneSrc& src, uint32_t gi) {
   MiPdschDesc pd{};
   pd.tm = src.tm2 ? 2 : 1;
@@ -162,9 +192,9 @@ __device__ __forceinline__ float fused_llr(const RmFuse& f, const MiLaneSrc& src
   const uint32_t* re = f.re_tab + src.re;
   const uint32_t* scr = f.scr_tab + src.scr;
   switch (src.qm) {
-    case 2: return demap_llr<2>(pd, gi, g, c0, c1, re, scr, f.noise);
-    case 4: return demap_llr<4>(pd, gi, g, c0, c1, re, scr, f.noise);
-    default: return demap_llr<6>(pd, gi, g, c0, c1, re, scr, f.noise);
+    case 2: return demap_llr<2, NRX>(pd, gi, g, c0, c1, re, scr, f.noise, f.grid_rx, f.ce_rx);
+    case 4: return demap_llr<4, NRX>(pd, gi, g, c0, c1, re, scr, f.noise, f.grid_rx, f.ce_rx);
+    default: return demap_llr<6, NRX>(pd, gi, g, c0, c1, re, scr, f.noise, f.grid_rx, f.ce_rx);
   }
 }
 
@@ -172,8 +202,11 @@ __device__ __forceinline__ float fused_llr(const RmFuse& f, const MiLaneSrc& src
 // NW / DIR: wavefronts per workgroup; DIR = every item is a direct group's chunk (those run
 // as 8-wavefront workgroups -- the same tile, each wavefront staging 8 rows and storing 16 ranks -- in a
 // launch of their own, whose instantiation carries none of the general combine's registers)
-template <bool FUSED, int FQ = 0, bool FT = false, int NW = RM_NW, bool DIR = false>
-__global__ __launch_bounds__(64 * NW, DIR ? RM_DIRECT_WPE : (NW == 8 ? RM_GENERAL_WPE : 1)) void rm_combine_kernel(const float* __restrict__ e, float* __restrict__ sb,
+// NRX: receive antennas the fused staging combines (RmFuse grid_rx / ce_rx); with two, every form computes one unit
+// after the other, accumulating antenna by antenna (the software pipeline would hold both antennas' values of two
+// units in flight)
+template <bool FUSED, int FQ = 0, bool FT = false, int NW = RM_NW, bool DIR = false, int NRX = 1>
+__global__ __launch_bounds__(64 * NW, rm_wpe(DIR, NW, NRX)) void rm_combine_kernel(const float* __restrict__ e, float* __restrict__ sb,
                                                         const MiGroupDesc* __restrict__ groups,
                                                         const MiLaneDesc* __restrict__ lanes,
                                                         const uint32_t* __restrict__ kdata, RmFuse fz,
@@ -304,13 +337,13 @@ __global__ __launch_bounds__(64 * NW, DIR ? RM_DIRECT_WPE : (NW == 8 ? RM_GENERA
       }
       return lo;
     };
-    if constexpr (FQ != 0 && DIR) {
+    if constexpr (FQ != 0 && (DIR || NRX > 1)) {
       // direct 8-wavefront form: ~3 units per thread, one unit after the other; occupancy hides latency (the
       // three-stage pipeline below measured 2.44-2.49 ms against 2.34-2.40 here, same box)
       for (uint32_t fi = q; fi < total; fi += 64) {
         const uint32_t lo = locate(fi), l = w + NW * (lo >> 1);
-        fused_unit<FQ, FT>(fz, s_src[l], rs_u0[w][lo] + (fi - rs_pre[w][lo]), rs_ga[w][lo], rs_gb[w][lo], rs_ta[w][lo],
-                           tile[l]);
+        fused_unit<FQ, FT, NRX>(fz, s_src[l], rs_u0[w][lo] + (fi - rs_pre[w][lo]), rs_ga[w][lo], rs_gb[w][lo],
+                                rs_ta[w][lo], tile[l]);
       }
     } else if constexpr (FQ != 0) {
       // uniform modulation: three-stage software pipeline over the thread's units (fi, fi + 64, ...):
@@ -347,8 +380,8 @@ __global__ __launch_bounds__(64 * NW, DIR ? RM_DIRECT_WPE : (NW == 8 ? RM_GENERA
     } else {
       for (uint32_t fi = q; fi < total; fi += 64) {
         const uint32_t lo = locate(fi), l = w + NW * (lo >> 1);
-        fused_unit_any(fz, s_src[l], rs_u0[w][lo] + (fi - rs_pre[w][lo]), rs_ga[w][lo], rs_gb[w][lo], rs_ta[w][lo],
-                       tile[l]);
+        fused_unit_any<NRX>(fz, s_src[l], rs_u0[w][lo] + (fi - rs_pre[w][lo]), rs_ga[w][lo], rs_gb[w][lo], rs_ta[w][lo],
+                            tile[l]);
       }
     }
   } else {
@@ -427,7 +460,7 @@ __global__ __launch_bounds__(64 * NW, DIR ? RM_DIRECT_WPE : (NW == 8 ? RM_GENERA
       if (j < E) { v = v + tile[lane][t]; c = true; }
       if (rep) {
         if constexpr (FUSED) {
-          for (j += nv; j < E; j += nv) v = v + fused_llr(fz, s_src[lane], (uint32_t)s_eoff[lane] + j);
+          for (j += nv; j < E; j += nv) v = v + fused_llr<NRX>(fz, s_src[lane], (uint32_t)s_eoff[lane] + j);
         } else {
           for (j += nv; j < E; j += nv) v = v + e[ld.e_off + j];
         }
@@ -556,24 +589,31 @@ void launch_rm_fused(const float2* grid, const float2* ce, const MiLaneSrc* lane
                      const uint32_t* scr_tab, float noise, float* sb, const MiGroupDesc* groups, const MiLaneDesc* lanes,
                      const MiKTab* ktabs, const uint32_t* ktab_data, uint32_t n_groups, uint32_t max_ncb, uint32_t unit_kind,
                      const uint32_t* items, const uint4* recs, uint32_t n_busy, uint32_t n_dbusy, uint32_t n_items,
-                     bool compact_ce, hipStream_t st) {
+                     bool compact_ce, const RxPlanes& rx, hipStream_t st) {
   if (!n_groups) return;
   if (items && !n_busy) items = nullptr;
   rm_idle(sb, groups, lanes, items, n_busy, n_items, ktabs, ktab_data, st);
-  const RmFuse fz{grid, ce, lane_src, re_tab, scr_tab, noise, (uint32_t)compact_ce};
+  const RmFuse fz{grid, ce, lane_src, re_tab, scr_tab, noise, (uint32_t)compact_ce, rx.grid, rx.ce};
+  const bool rx2 = rx.n == 2;
   uint32_t skip = 0;
   if (items && n_dbusy) {
 #define MI_RM_LAUNCH(...) \
   hipLaunchKernelGGL((__VA_ARGS__), dim3(n_dbusy), dim3(512), 0, st, nullptr, sb, groups, lanes, ktab_data, fz, items, \
                      recs, ktabs)
+// the instantiation for the batch's antenna count
+#define MI_RM_LAUNCH2(...)                                            \
+  do {                                                                \
+    if (rx2) MI_RM_LAUNCH(rm_combine_kernel<__VA_ARGS__, 2>);         \
+    else MI_RM_LAUNCH(rm_combine_kernel<__VA_ARGS__, 1>);             \
+  } while (0)
     switch (unit_kind) {   // Qm + 8 * (TM2)
-      case 2: MI_RM_LAUNCH(rm_combine_kernel<true, 2, false, 8, true>); break;
-      case 4: MI_RM_LAUNCH(rm_combine_kernel<true, 4, false, 8, true>); break;
-      case 6: MI_RM_LAUNCH(rm_combine_kernel<true, 6, false, 8, true>); break;
-      case 10: MI_RM_LAUNCH(rm_combine_kernel<true, 2, true, 8, true>); break;
-      case 12: MI_RM_LAUNCH(rm_combine_kernel<true, 4, true, 8, true>); break;
-      case 14: MI_RM_LAUNCH(rm_combine_kernel<true, 6, true, 8, true>); break;
-      default: MI_RM_LAUNCH(rm_combine_kernel<true, 0, false, 8, true>); break;
+      case 2: MI_RM_LAUNCH2(true, 2, false, 8, true); break;
+      case 4: MI_RM_LAUNCH2(true, 4, false, 8, true); break;
+      case 6: MI_RM_LAUNCH2(true, 6, false, 8, true); break;
+      case 10: MI_RM_LAUNCH2(true, 2, true, 8, true); break;
+      case 12: MI_RM_LAUNCH2(true, 4, true, 8, true); break;
+      case 14: MI_RM_LAUNCH2(true, 6, true, 8, true); break;
+      default: MI_RM_LAUNCH2(true, 0, false, 8, true); break;
     }
 #undef MI_RM_LAUNCH
     skip = n_dbusy;
@@ -587,15 +627,16 @@ void launch_rm_fused(const float2* grid, const float2* ce, const MiLaneSrc* lane
                      it, rc, ktabs)
   constexpr int GNW = RM_GENERAL_NW;
   switch (unit_kind) {   // Qm + 8 * (TM2)
-    case 2: MI_RM_LAUNCH(rm_combine_kernel<true, 2, false, GNW>); break;
-    case 4: MI_RM_LAUNCH(rm_combine_kernel<true, 4, false, GNW>); break;
-    case 6: MI_RM_LAUNCH(rm_combine_kernel<true, 6, false, GNW>); break;
-    case 10: MI_RM_LAUNCH(rm_combine_kernel<true, 2, true, GNW>); break;
-    case 12: MI_RM_LAUNCH(rm_combine_kernel<true, 4, true, GNW>); break;
-    case 14: MI_RM_LAUNCH(rm_combine_kernel<true, 6, true, GNW>); break;
-    default: MI_RM_LAUNCH(rm_combine_kernel<true, 0, false, GNW>); break;
+    case 2: MI_RM_LAUNCH2(true, 2, false, GNW, false); break;
+    case 4: MI_RM_LAUNCH2(true, 4, false, GNW, false); break;
+    case 6: MI_RM_LAUNCH2(true, 6, false, GNW, false); break;
+    case 10: MI_RM_LAUNCH2(true, 2, true, GNW, false); break;
+    case 12: MI_RM_LAUNCH2(true, 4, true, GNW, false); break;
+    case 14: MI_RM_LAUNCH2(true, 6, true, GNW, false); break;
+    default: MI_RM_LAUNCH2(true, 0, false, GNW, false); break;
   }
 #undef MI_RM_LAUNCH
+#undef MI_RM_LAUNCH2
 }
 
 }  // namespace mi
