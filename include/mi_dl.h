@@ -32,7 +32,8 @@ typedef struct {
   uint32_t nof_ports;    /* 1 or 2 CRS ports */
   uint32_t sf_idx;       /* 0..9 */
   uint32_t cfi;          /* 1..3 (control symbols) */
-  uint32_t tm;           /* 1 = single port, 2 = transmit diversity (SFBC) */
+  uint32_t tm;           /* 1 = single port, 2 = transmit diversity (SFBC), 3 = open-loop spatial multiplexing
+                          * (large-delay CDD), 4 = closed-loop spatial multiplexing: two layers, two codewords (below) */
   uint32_t nl_td;        /* N_L used by rate matching for TM2 (36.212 5.1.4.1.2: 2) */
   uint32_t rnti;
   uint32_t rv;           /* redundancy version 0..3 */
@@ -43,6 +44,16 @@ typedef struct {
    * Otherwise bit 0 / bit 1 of entry p = PRB p used in slot 0 / slot 1 (distributed VRB, 36.211 6.2.3.2:
    * srslte_ra_dl_grant_t.prb_idx[0] / [1]); the RE gather follows 36.211 6.3.5 per slot. */
   uint8_t  prb_mask[MI_DL_MAX_PRB];
+  /* Spatial multiplexing (tm 3 / 4; both 0 for tm 1 / 2, where a zeroed pair plans exactly as before the fields
+   * existed).  A spatially multiplexed subframe -- 2 CRS ports, 2 receive antennas, 2 layers, one codeword per layer --
+   * is TWO consecutive entries of the cfg array: entry i with cw = 0 and entry i + 1 with cw = 1, both with the same
+   * cell, sf_idx, cfi, tm, pmi, rnti and prb_mask, each with its own tbs, Qm, rv and new_tb (nl_td is ignored:
+   * N_L = 1 per codeword).  The cw = 1 entry is a transport block of its own everywhere after the LLRs (LLR range,
+   * code blocks, softbuffer rows, payload, tb_crc, tb_its) but owns no samples: its IQ / grid / ce offsets are its
+   * partner's, it adds nothing to mi_dl_batch_iq_samples or the grid / ce buffers, the front end runs once per
+   * physical subframe and its MI_DL_BUF_METRICS row is never written. */
+  uint32_t cw;           /* codeword q of the entry: 0 or 1 */
+  uint32_t pmi;          /* tm 4: two-layer codebook index 1 or 2 (36.211 Table 6.3.4.2.3-1); ignored for tm 3 */
 } mi_dl_sf_cfg_t;
 
 /* stages, for mi_dl_batch_stage_ms */
@@ -124,7 +135,15 @@ mi_dl_batch_t *mi_dl_batch_create(const mi_dl_sf_cfg_t *cfgs, uint32_t n_sf, uin
  * mi_dl_batch_bytes / _upload / _download / _device_ptr cover all planes.  The strides follow a re-plan.
  * MI_DL_FLAG_IQ_SC16, MI_DL_FLAG_CE_COMPACT and MI_DL_FLAG_KEEP_LLR work as with one antenna (the LLR stream is the
  * combined one).  mi_dl_ctrl_* and mi_pbch_* on a two-antenna batch read antenna 0 (plane 0): the control channels
- * are not combined.  The per-TTI srslte_ue_dl_* API stays single-antenna. */
+ * are not combined.  The per-TTI srslte_ue_dl_* API stays single-antenna.
+ * Spatial multiplexing (tm 3 / 4 entry pairs, mi_dl_sf_cfg_t): only on a batch, pipe or re-plan with n_rx = 2 (else
+ * NULL / -1 and mi_last_error).  The pair's two layers are detected per RE over both antennas,
+ *   x^ = (G^H G + noise I)^-1 G^H y,  G = H P_i,  H[a][p] = antenna a's estimate of port p,  noise = 0.01,
+ * P_i = (1/2) [[1, 1], [w, -w]] at RE i of the PDSCH mapping order with w = (-1)^i (tm 3), 1 / j (tm 4 pmi 1 / 2), then
+ * demapped and descrambled per codeword (c_init with q 2^13) into the two entries' LLR ranges.  A run of a plan that
+ * holds a pair is never fused: DEMAP writes the LLR stream and RM reads it, as with MI_DL_FLAG_KEEP_LLR, and
+ * MI_DL_FLAG_CE_COMPACT is inert.  mi_dl_batch_iq_offset and mi_dl_batch_offset(GRID | CE) of a cw = 1 entry return its
+ * partner's values; its MI_DL_BUF_METRICS row is never written.  TM1 / TM2 entries may share the batch. */
 mi_dl_batch_t *mi_dl_batch_create_rx(const mi_dl_sf_cfg_t *cfgs, uint32_t n_sf, uint32_t n_rx, uint32_t max_its,
                                      uint32_t flags);
 uint32_t mi_dl_batch_n_rx(const mi_dl_batch_t *b);
@@ -246,6 +265,13 @@ int    mi_turbo_encode(const uint8_t *bits, uint32_t K, uint32_t F, uint8_t *d);
  * channel h and AWGN at snr_db per RE (>= 200 => noiseless).  iq: 2 * 15 N floats. */
 int    mi_tx_subframe(const mi_dl_sf_cfg_t *cfg, const uint8_t *tb, const float *h_re_im /* 2*ports */,
                       float snr_db, uint64_t noise_seed, float *iq);
+/* The same for a spatially multiplexed subframe (tm 3 / 4): cfg_pair = its cw 0 and cw 1 entries, tb0 / tb1 their
+ * transport blocks.  Per-codeword scrambling (c_init with q 2^13), layer mapping x0 = d0, x1 = d1, precoding
+ * [y_port0; y_port1] = P_i [x0; x1] with P_i = (1/2) [[1, 1], [w, -w]] at RE i of the PDSCH mapping order: w = (-1)^i
+ * for tm 3 (W D(i) U, 36.211 6.3.4.2.2), 1 / j for tm 4 pmi 1 / 2 (6.3.4.2.3); CRS and PCFICH as mi_tx_subframe.  h: one
+ * receive antenna's flat channel per port; call once per receive antenna (own h, own noise seed). */
+int    mi_tx_subframe_sm(const mi_dl_sf_cfg_t *cfg_pair, const uint8_t *tb0, const uint8_t *tb1,
+                         const float *h_re_im /* 2*2 */, float snr_db, uint64_t noise_seed, float *iq);
 int    mi_sf_len(uint32_t nof_prb);
 /* number of PDSCH bits G of a configuration (RE count x Qm, 36.211 6.3.5 / 6.4) */
 int    mi_pdsch_G(const mi_dl_sf_cfg_t *cfg);

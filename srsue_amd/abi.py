@@ -36,12 +36,14 @@ class SfCfg(C.Structure):
     """mi_dl_sf_cfg_t (include/mi_dl.h)."""
     _fields_ = [(n, C.c_uint32) for n in ("cell_id", "nof_prb", "nof_ports", "sf_idx", "cfi", "tm", "nl_td",
                                           "rnti", "rv", "tbs", "Qm", "new_tb")] + \
-               [("prb_mask", C.c_uint8 * MAX_PRB)]
+               [("prb_mask", C.c_uint8 * MAX_PRB), ("cw", C.c_uint32), ("pmi", C.c_uint32)]
 
 
 def sf_cfg(cell_id=1, nof_prb=100, nof_ports=1, sf_idx=1, cfi=1, tm=None, rnti=0x46, rv=0, tbs=75376, Qm=6,
-           new_tb=1, prb=None, nl_td=2):
+           new_tb=1, prb=None, nl_td=2, cw=0, pmi=0):
+    """cw / pmi: spatial multiplexing (tm 3 / 4), where a subframe is two consecutive entries cw = 0, cw = 1."""
     c = SfCfg()
+    c.cw, c.pmi = cw, pmi
     c.cell_id, c.nof_prb, c.nof_ports, c.sf_idx, c.cfi = cell_id, nof_prb, nof_ports, sf_idx, cfi
     c.tm = tm if tm is not None else (2 if nof_ports == 2 else 1)
     c.nl_td, c.rnti, c.rv, c.tbs, c.Qm, c.new_tb = nl_td, rnti, rv, tbs, Qm, new_tb
@@ -108,6 +110,7 @@ def lib():
             "mi_dl_batch_device_bytes": (sz, [vp]),
             "mi_dl_plan_device_bytes": (sz, [vp, u32, u32]),
             "mi_tx_subframe": (C.c_int, [vp, vp, vp, C.c_float, C.c_uint64, vp]),
+            "mi_tx_subframe_sm": (C.c_int, [vp, vp, vp, vp, C.c_float, C.c_uint64, vp]),
             "mi_turbo_encode": (C.c_int, [vp, u32, u32, vp]),
             "mi_tdec_create": (vp, [u32, u32, u32, C.c_int, C.c_int, u32]),
             "mi_tdec_destroy": (None, [vp]),
@@ -216,7 +219,7 @@ def lib():
         }
         # the receive-diversity entry points are absent from a library built before them, which an A/B run selects
         # with SRSUE_AMD_LIB (tools/ab_libs.sh): such a library binds without them, and calling one raises
-        rx_names = {n for n in sig if n.endswith("_rx") or "_rx_" in n or n == "mi_dl_batch_n_rx"}
+        rx_names = {n for n in sig if n.endswith("_rx") or "_rx_" in n or n in ("mi_dl_batch_n_rx", "mi_tx_subframe_sm")}
         for name, (res, args) in sig.items():
             if name in rx_names and "SRSUE_AMD_LIB" in os.environ and not hasattr(L, name):
                 continue
@@ -244,6 +247,14 @@ def emu():
         E.emu_payload_offset.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         E.emu_pdsch_llr_rx.restype = C.c_int
         E.emu_pdsch_llr_rx.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        E.emu_softbuffer.restype = C.c_size_t
+        E.emu_softbuffer.argtypes = [C.c_void_p]
+        E.emu_plan_info.restype = C.c_int
+        E.emu_plan_info.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        E.emu_last_error.restype = C.c_char_p
+        E.emu_last_error.argtypes = []
+        E.emu_pdsch_llr_sm.restype = C.c_int
+        E.emu_pdsch_llr_sm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         _emu = E
     return _emu
 
@@ -280,6 +291,25 @@ def tx_subframe(cfg, tb_bytes, h=None, snr_db=30.0, seed=0xA5A5):
                               float(snr_db), seed, iq.ctypes.data)
     if rc:
         raise RuntimeError("mi_tx_subframe failed")
+    return iq
+
+
+def tx_subframe_sm(cfg_pair, tb0, tb1, h=None, snr_db=30.0, seed=0xA5A5):
+    """One receive antenna's samples of a spatially multiplexed subframe (mi_tx_subframe_sm): cfg_pair = its cw 0 and
+    cw 1 entries, h = that antenna's flat channel per port.  Call once per receive antenna."""
+    n = lib().mi_sf_len(cfg_pair[0].nof_prb)
+    iq = np.zeros(2 * n, np.float32)
+    hh = None
+    if h is not None:
+        hh = np.zeros(4, np.float32)
+        for p, v in enumerate(h[:2]):
+            hh[2 * p], hh[2 * p + 1] = v.real, v.imag
+    arr = cfg_array(list(cfg_pair))
+    t0, t1 = np.ascontiguousarray(tb0, np.uint8), np.ascontiguousarray(tb1, np.uint8)
+    rc = lib().mi_tx_subframe_sm(C.cast(arr, C.c_void_p), t0.ctypes.data, t1.ctypes.data,
+                                 None if hh is None else hh.ctypes.data, float(snr_db), seed, iq.ctypes.data)
+    if rc:
+        raise RuntimeError("mi_tx_subframe_sm failed")
     return iq
 
 

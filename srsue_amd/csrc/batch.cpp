@@ -16,6 +16,13 @@ static bool n_rx_ok(uint32_t n_rx, const char* who) {
   return false;
 }
 
+// a plan with spatial multiplexing pairs (tm 3 / 4) detects over two receive antennas: refused on any other batch
+static bool sm_rx_ok(const mi::PlanData& p, uint32_t n_rx, const char* who) {
+  if (p.sm.empty() || n_rx == 2) return true;
+  mi::set_error(std::string(who) + ": spatial multiplexing (tm 3 / 4) needs n_rx = 2 receive antennas");
+  return false;
+}
+
 mi_dl_batch_t* mi_dl_batch_create(const mi_dl_sf_cfg_t* cfgs, uint32_t n_sf, uint32_t max_its, uint32_t flags) {
   return mi_dl_batch_create_rx(cfgs, n_sf, 1, max_its, flags);
 }
@@ -29,7 +36,8 @@ mi_dl_batch_t* mi_dl_batch_create_rx(const mi_dl_sf_cfg_t* cfgs, uint32_t n_sf, 
   b->eng.max_its = max_its ? max_its : 4;
   b->eng.flags = flags;
   b->eng.n_rx = n_rx;
-  if (!mi::hip_ok(hipGetDevice(&b->eng.device), "device") || b->eng.plan.build(cfgs, n_sf, true) || b->eng.upload(nullptr, true) ||
+  if (!mi::hip_ok(hipGetDevice(&b->eng.device), "device") || b->eng.plan.build(cfgs, n_sf, true) ||
+      !sm_rx_ok(b->eng.plan, n_rx, "mi_dl_batch_create_rx") || b->eng.upload(nullptr, true) ||
       !mi::hip_ok(hipStreamSynchronize(nullptr), "upload sync")) {
     delete b;
     return nullptr;
@@ -202,6 +210,7 @@ int mi_dl_plan_build(mi_dl_plan_t* p, const mi_dl_sf_cfg_t* cfgs, uint32_t n_sf)
 
 int mi_dl_batch_replan(mi_dl_batch_t* b, mi_dl_plan_t* p, void* stream) {
   if (!b || !p || !p->built) { mi::set_error("mi_dl_batch_replan: no built plan"); return -1; }
+  if (!sm_rx_ok(p->plan, b->eng.n_rx, "mi_dl_batch_replan")) return -1;   // the batch keeps its plan
   const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // the table upload rewrites what a pending split run's back end reads
   if (!b->eng.order_after_split(st)) return -1;

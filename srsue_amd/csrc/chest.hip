@@ -24,17 +24,17 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return s;
 }
 
-__global__ __launch_bounds__(256) void chest_kernel(const float2* __restrict__ grid, float2* __restrict__ ce,
-                                                   const MiSfDesc* __restrict__ sfs,
-                                                   const MiCellDesc* __restrict__ cells,
-                                                   const float2* __restrict__ crs, float* __restrict__ metrics,
-                                                   uint32_t compact, size_t grid_rx, size_t ce_rx) {
+// subframe sf of the batch's n_sf (the metrics rows' stride), antenna blockIdx.y
+__device__ __forceinline__ void chest_sf(const float2* __restrict__ grid, float2* __restrict__ ce,
+                                         const MiSfDesc* __restrict__ sfs, const MiCellDesc* __restrict__ cells,
+                                         const float2* __restrict__ crs, float* __restrict__ metrics, uint32_t compact,
+                                         size_t grid_rx, size_t ce_rx, uint32_t sf, uint32_t n_sf) {
   constexpr int PL[4] = {0, 4, 7, 11};
   constexpr float W1 = 0.1f, W0 = 0.8f;
   __shared__ float2 hp[4][2 * NRB_MAX];
   __shared__ float2 hs[4][2 * NRB_MAX];
   __shared__ float red[4];
-  const MiSfDesc d = sfs[blockIdx.x];
+  const MiSfDesc d = sfs[sf];
   const MiCellDesc c = cells[d.cell];
   const int W = (int)c.W, NP = 2 * (int)c.nof_prb;
   // blockIdx.y: the receive antenna (its grid / estimate planes grid_rx / ce_rx elements apart)
@@ -118,17 +118,43 @@ __global__ __launch_bounds__(256) void chest_kernel(const float2* __restrict__ g
   rssi = block_sum(rssi, red);
   if (threadIdx.x == 0) {
     const float rs = rsrp / (float)(4 * NP), no = noise / (float)(4 * NP * c.nof_ports), ri = rssi / 4.0f;
-    float* m = metrics + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 5;   // [antenna][subframe][5]
+    float* m = metrics + ((size_t)blockIdx.y * n_sf + sf) * 5;   // [antenna][subframe][5]
     m[0] = rs; m[1] = ri; m[2] = ri > 0.f ? (float)c.nof_prb * rs / ri : 0.f;
     m[3] = no; m[4] = no > 0.f ? rs / no : 0.f;
   }
 }
 
+// every subframe of the batch: workgroup x estimates subframe x
+__global__ __launch_bounds__(256) void chest_kernel(const float2* __restrict__ grid, float2* __restrict__ ce,
+                                                   const MiSfDesc* __restrict__ sfs,
+                                                   const MiCellDesc* __restrict__ cells,
+                                                   const float2* __restrict__ crs, float* __restrict__ metrics,
+                                                   uint32_t compact, size_t grid_rx, size_t ce_rx) {
+  chest_sf(grid, ce, sfs, cells, crs, metrics, compact, grid_rx, ce_rx, blockIdx.x, gridDim.x);
+}
+
+// the listed subframes only (a batch with codeword pairs: each physical subframe once, Plan::phys); the metrics rows
+// stay indexed by subframe, the rows of the entries left out are not written
+__global__ __launch_bounds__(256) void chest_list_kernel(const float2* __restrict__ grid, float2* __restrict__ ce,
+                                                        const MiSfDesc* __restrict__ sfs,
+                                                        const MiCellDesc* __restrict__ cells,
+                                                        const float2* __restrict__ crs, float* __restrict__ metrics,
+                                                        uint32_t compact, size_t grid_rx, size_t ce_rx,
+                                                        const uint32_t* __restrict__ list, uint32_t n_sf) {
+  chest_sf(grid, ce, sfs, cells, crs, metrics, compact, grid_rx, ce_rx, list[blockIdx.x], n_sf);
+}
+
 void launch_chest(const float2* grid, float2* ce, const MiSfDesc* sfs, const MiCellDesc* cells, const float2* crs,
-                  float* metrics, uint32_t n_sf, const RxPlanes& rx, hipStream_t st, bool compact) {
-  if (!n_sf) return;
-  hipLaunchKernelGGL(chest_kernel, dim3(n_sf, rx.n), dim3(256), 0, st, grid, ce, sfs, cells, crs, metrics,
-                     (uint32_t)compact, rx.grid, rx.ce);
+                  float* metrics, uint32_t n_sf, const RxPlanes& rx, hipStream_t st, bool compact, const uint32_t* list,
+                  uint32_t n_list) {
+  if (!list) {
+    if (!n_sf) return;
+    hipLaunchKernelGGL(chest_kernel, dim3(n_sf, rx.n), dim3(256), 0, st, grid, ce, sfs, cells, crs, metrics,
+                       (uint32_t)compact, rx.grid, rx.ce);
+  } else if (n_list) {
+    hipLaunchKernelGGL(chest_list_kernel, dim3(n_list, rx.n), dim3(256), 0, st, grid, ce, sfs, cells, crs, metrics,
+                       (uint32_t)compact, rx.grid, rx.ce, list, n_sf);
+  }
 }
 
 }  // namespace mi

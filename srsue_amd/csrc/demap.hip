@@ -13,22 +13,6 @@
 
 namespace mi {
 
-template <int QM>
-__device__ __forceinline__ void demap_store(float2 x, const uint32_t* __restrict__ scr, uint32_t bit0,
-                                            float* __restrict__ out) {
-  float l[QM];
-  demap_dim<QM>(x.x, l);
-  demap_dim<QM>(x.y, l + 1);
-#pragma unroll
-  for (int b = 0; b < QM; b++) {
-    const uint32_t i = bit0 + b;
-    if ((scr[i >> 5] >> (i & 31)) & 1u) l[b] = -l[b];
-  }
-  float2* o = reinterpret_cast<float2*>(out + bit0);
-#pragma unroll
-  for (int b = 0; b < QM; b += 2) o[b / 2] = make_float2(l[b], l[b + 1]);
-}
-
 // antenna a's grid at g + a g_rx, its estimates at c0 / c1 + a c_rx (the batch's antenna planes)
 template <int QM, int NRX>
 __device__ __forceinline__ void demap_unit(const MiPdschDesc& pd, uint32_t u, const float2* __restrict__ g,
@@ -87,6 +71,7 @@ __global__ __launch_bounds__(256) void demap_kernel(const float2* __restrict__ g
                                                    size_t c_rx) {
   const MiSfDesc d = sfs[blockIdx.y];
   const MiPdschDesc pd = pds[d.pdsch];
+  if (pd.tm > 2) return;   // spatial multiplexing entries: sm_detect_kernel writes their LLRs (sm_detect.hip)
   const uint32_t units = pd.tm == 2 ? pd.nre / 2 : pd.nre;
   const uint32_t u = blockIdx.x * 256 + threadIdx.x;
   if (u >= units) return;

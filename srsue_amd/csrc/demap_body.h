@@ -149,6 +149,24 @@ __device__ __forceinline__ void demap_dim(float x, float* llr) {
   }
 }
 
+// the QM LLRs of one equalised symbol, descrambled (scr bit bit0 + b set: sign flipped), to out[bit0 ..] as float2
+// stores (QM and bit0 are even, the stream's base is 16-B aligned)
+template <int QM>
+__device__ __forceinline__ void demap_store(float2 x, const uint32_t* __restrict__ scr, uint32_t bit0,
+                                            float* __restrict__ out) {
+  float l[QM];
+  demap_dim<QM>(x.x, l);
+  demap_dim<QM>(x.y, l + 1);
+#pragma unroll
+  for (int b = 0; b < QM; b++) {
+    const uint32_t i = bit0 + b;
+    if ((scr[i >> 5] >> (i & 31)) & 1u) l[b] = -l[b];
+  }
+  float2* o = reinterpret_cast<float2*>(out + bit0);
+#pragma unroll
+  for (int b = 0; b < QM; b += 2) o[b / 2] = make_float2(l[b], l[b + 1]);
+}
+
 // LLR of bit j (MSB first) of one dimension: demap_dim's arithmetic for that bit alone (no dynamic
 // register-array index)
 template <int QM>

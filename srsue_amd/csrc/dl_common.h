@@ -129,6 +129,16 @@ struct MiLaneSrc {           // one per code block: where the fused demap stage 
   uint32_t wdiv;             // floor(2^32 / W) + 1: RE index / W = __umulhi(re, wdiv) (compact estimates)
 };
 
+struct MiSmDesc {            // one per spatially multiplexed subframe (a cw 0 / cw 1 pair of entries): sm_detect.hip
+  uint64_t goff, coff;       // float2 offsets of the subframe's grid and of its port-0 channel estimates (antenna 0)
+  uint64_t e0, e1;           // float offsets of codeword 0's and codeword 1's LLRs
+  uint32_t c1;               // port 1's estimates at coff + c1 (NSYMB x W)
+  uint32_t re, nre;          // the PDSCH RE list (mapping order: the layer index i is the position in it) and its length
+  uint32_t scr0, scr1;       // the codewords' scrambling words
+  uint32_t qm0, qm1;         // bits per symbol of each codeword
+  uint32_t mode;             // precoder (sm_body.h): 0 = TM3 large-delay CDD, 1 / 2 = TM4 codebook index 1 / 2
+};
+
 struct MiGroupDesc {         // one per wavefront group of <= 64 code blocks of equal K
   uint32_t K, Ncb;
   uint32_t lane0;            // first MiLaneDesc index (64 consecutive entries)

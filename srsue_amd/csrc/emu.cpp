@@ -16,6 +16,7 @@
 #include "kernels_consts.h"
 #include "plan.h"
 #include "rm_body.h"
+#include "sm_body.h"
 #include "tb_body.h"
 #include "tdec_body.h"
 #include "tdec_p2_body.h"
@@ -121,6 +122,11 @@ static mi::TdecLaneResult emu_win_cb(const MiGroupDesc& g, const MiKTab& kt, con
 static int g_keep_sb = 0;
 static std::vector<float> g_sb;
 extern "C" void emu_keep_softbuffer(int on) { g_keep_sb = on; g_sb.clear(); }
+// the kept arena (the layout of MI_DL_BUF_SOFTBUFFER): its size in floats; copied to out when out is not null
+extern "C" size_t emu_softbuffer(float* out) {
+  if (out && !g_sb.empty()) memcpy(out, g_sb.data(), g_sb.size() * sizeof(float));
+  return g_sb.size();
+}
 
 extern "C" int emu_decode_llr(const mi_dl_sf_cfg_t* cfgs, uint32_t n, const float* llr_concat, uint32_t max_its,
                               uint8_t* payload, uint32_t* tb_ok, uint32_t* tb_its, uint32_t* cb_its) {
@@ -372,6 +378,51 @@ extern "C" int emu_pdsch_llr_rx(const mi_dl_sf_cfg_t* cfg, uint32_t n_rx, const 
   if (n_rx == 2) emu_llr_run<2>(pd, g, c0, W, re, scr, noise, g_rx, c_rx, out);
   else emu_llr_run<1>(pd, g, c0, W, re, scr, noise, g_rx, c_rx, out);
   return (int)pd.G;
+}
+
+// What the planner lays out for entry sf of a batch (tests/test_sm_plan.py): out[0..3] = its IQ, grid, ce and LLR
+// offsets, [4] G, [5] RE count, [6] code blocks, [7] / [8] / [9] the sum, smallest and largest E of its code blocks,
+// [10] payload offset, [11] 1 when an FFT list holds it, then the batch's totals: [12] IQ samples, [13] grid and
+// [14] ce elements, [15] LLR floats, [16] FFT list entries, [17] channel-estimation list entries (0 = every entry),
+// [18] codeword pairs, [19] the largest demap unit count.  Returns 0, -1 when the planner refuses (emu_last_error).
+extern "C" int emu_plan_info(const mi_dl_sf_cfg_t* cfgs, uint32_t n, uint32_t sf, uint64_t* out) {
+  mi::Plan P;
+  if (P.build(cfgs, n, true) || sf >= n) return -1;
+  const MiSfDesc& sd = P.sfs[sf];
+  const MiPdschDesc& pd = P.pds[sd.pdsch];
+  uint64_t sum = 0, lo = ~0ull, hi = 0;
+  for (const MiLaneDesc& ld : P.lanes)
+    if (ld.valid && ld.tb == sf) {
+      sum += ld.E;
+      lo = std::min<uint64_t>(lo, ld.E);
+      hi = std::max<uint64_t>(hi, ld.E);
+    }
+  const bool in_fft = std::find(P.fft_list_flat.begin(), P.fft_list_flat.end(), sf) != P.fft_list_flat.end();
+  const uint64_t v[20] = {sd.iq_off, sd.grid_off, sd.ce_off, sd.e_off, pd.G, pd.nre, P.tbs[sf].C, sum, lo, hi,
+                          P.tbs[sf].pay_off, in_fft, P.iq_samples, P.grid_elems, P.ce_elems, P.e_floats,
+                          P.fft_list_flat.size(), P.phys.size(), P.sm.size(), P.max_units};
+  memcpy(out, v, sizeof(v));
+  return 0;
+}
+extern "C" const char* emu_last_error() { return mi::last_error(); }
+
+// The LLRs of both codewords of one spatially multiplexed subframe (cfg_pair: its cw 0 and cw 1 entries) from the two
+// antennas' grids ([2][14][W] float2) and channel estimates ([2][2][14][W] float2): sm_body.h sm_detect_re -- the
+// arithmetic of sm_detect_kernel -- RE by RE over the planner's pair descriptor.  out0 / out1: nre Qm0 and nre Qm1
+// floats.  Returns nre, -1 on a configuration the planner refuses.
+extern "C" int emu_pdsch_llr_sm(const mi_dl_sf_cfg_t* cfg_pair, const float* grids, const float* ces, float noise,
+                                float* out0, float* out1) {
+  mi::Plan P;
+  if (P.build(cfg_pair, 2, true) || P.sm.size() != 1) return -1;
+  const MiSmDesc& d = P.sm[0];
+  const size_t W = 12 * (size_t)cfg_pair->nof_prb, g_rx = (size_t)mi::NSYMB * W, c_rx = 2 * g_rx;
+  std::vector<float> e(P.e_floats, 0.f);
+  for (uint32_t i = 0; i < d.nre; i++)
+    mi::sm_detect_re(d, i, reinterpret_cast<const float2*>(grids) + d.goff, reinterpret_cast<const float2*>(ces) + d.coff,
+                     P.re_tab.data(), P.scr_tab.data(), e.data(), noise, g_rx, c_rx);
+  memcpy(out0, &e[d.e0], (size_t)d.nre * d.qm0 * sizeof(float));
+  memcpy(out1, &e[d.e1], (size_t)d.nre * d.qm1 * sizeof(float));
+  return (int)d.nre;
 }
 
 // The packed decoder's trellis start (tdec_p2_body.h header, p2.h tadd_a): the LLRs of steps 0..2 taken from the start

@@ -110,7 +110,8 @@ size_t tab_span(size_t bytes) { return (std::max<size_t>(bytes, 1) + 255) & ~(si
                       tab(d_scr, P.scr_tab), tab(d_sfs, P.sfs), tab(d_lanes, P.lanes), tab(d_lanesrc, P.lane_src),   \
                       tab(d_groups, P.groups), tab(d_ktabs, P.ktabs), tab(d_kdata, P.kdata), tab(d_tbs, P.tbs),      \
                       tab(d_cblist, P.cb_list), tab(d_fftlist, P.fft_list_flat), tab(d_rmitems, P.rm_items),         \
-                      tab(d_rmrecs, P.rm_recs), tab(d_pairs, P.pairs), tab(d_rmdir, P.rm_direct)}
+                      tab(d_rmrecs, P.rm_recs), tab(d_pairs, P.pairs), tab(d_rmdir, P.rm_direct), tab(d_sm, P.sm),           \
+                      tab(d_phys, P.phys)}
 
 int Engine::stage_tables(DevBuf& arena, std::vector<size_t>& offs, hipStream_t st) {
   const Plan& P = plan;
@@ -328,8 +329,14 @@ int Engine::run(const void* d_iq, hipStream_t st, uint32_t mask, float* sb_overr
   // (channel estimation and the fused demap in one run), nothing else reads the full estimates, and no
   // code block repeats LLRs (the single-LLR repetition path reads full estimates)
   const uint32_t full = (1u << MI_DL_STAGE_CHEST) | (1u << MI_DL_STAGE_DEMAP) | (1u << MI_DL_STAGE_RM);
+  // a plan with spatial multiplexing pairs never fuses (below): the compact form has no consumer, the flag is inert
+  const bool has_sm = !P.sm.empty();
+  if (has_sm && n_rx != 2) {
+    set_error("spatial multiplexing (tm 3 / 4) needs a batch of n_rx = 2 receive antennas");
+    return -1;
+  }
   const bool compact = (flags & MI_DL_FLAG_CE_COMPACT) && !(flags & MI_DL_FLAG_KEEP_LLR) && P.has_pdsch &&
-                       (mask & full) == full && !P.rm_rep;
+                       (mask & full) == full && !P.rm_rep && !has_sm;
   // the demap stage (alone or fused into rate de-matching) reads the estimates; without a chest stage in
   // this run they must be full ones
   if (P.has_pdsch && ce_compact && !(mask & (1u << MI_DL_STAGE_CHEST)) && (mask & (1u << MI_DL_STAGE_DEMAP))) {
@@ -348,19 +355,26 @@ int Engine::run(const void* d_iq, hipStream_t st, uint32_t mask, float* sb_overr
   mark(1);
   if (mask & (1u << MI_DL_STAGE_CHEST))
     launch_chest(d_grid.as<float2>(), d_ce.as<float2>(), d_sfs.as<MiSfDesc>(), d_cells.as<MiCellDesc>(),
-                 d_crs.as<float2>(), d_metrics.as<float>(), nsf, rx, st, compact);
+                 d_crs.as<float2>(), d_metrics.as<float>(), nsf, rx, st, compact,
+                 P.phys.empty() ? nullptr : d_phys.as<uint32_t>(), (uint32_t)P.phys.size());
   if (mask & (1u << MI_DL_STAGE_CHEST)) ce_compact = compact;
   mark(2);
   if (P.has_pdsch) {
     float* sb = sb_override ? sb_override : d_sb.as<float>();
-    // fused demap -> rate de-matching unless the caller keeps the LLR stream (or supplies it)
+    // fused demap -> rate de-matching unless the caller keeps the LLR stream (or supplies it), or the plan holds a
+    // spatial multiplexing pair: detection writes the LLR stream of both codewords and rate de-matching reads it
     const bool fuse = (mask & (1u << MI_DL_STAGE_DEMAP)) && (mask & (1u << MI_DL_STAGE_RM)) &&
-                      !(flags & MI_DL_FLAG_KEEP_LLR);
+                      !(flags & MI_DL_FLAG_KEEP_LLR) && !has_sm;
     if (!fuse && (mask & ((1u << MI_DL_STAGE_DEMAP) | (1u << MI_DL_STAGE_RM))) && !ensure_llr()) return -1;
-    if ((mask & (1u << MI_DL_STAGE_DEMAP)) && !fuse)
+    if ((mask & (1u << MI_DL_STAGE_DEMAP)) && !fuse) {
+      // the TM1 / TM2 entries (demap_kernel returns at once on the others), then the pairs
       launch_demap(d_grid.as<float2>(), d_ce.as<float2>(), d_e.as<float>(), d_sfs.as<MiSfDesc>(),
                    d_pds.as<MiPdschDesc>(), d_cells.as<MiCellDesc>(), d_re.as<uint32_t>(), d_scr.as<uint32_t>(), nsf,
                    P.max_units, noise, rx, st);
+      if (has_sm)
+        launch_sm_detect(d_grid.as<float2>(), d_ce.as<float2>(), d_e.as<float>(), d_sm.as<MiSmDesc>(),
+                         (uint32_t)P.sm.size(), P.sm_max_nre, d_re.as<uint32_t>(), d_scr.as<uint32_t>(), noise, rx, st);
+    }
     mark(3);
     // the direct groups' row maps (Plan::rm_direct) before the combine kernel stages their chunks -- only in a
     // run that rate de-matches (a run without RM must leave the softbuffer, maps included, untouched)

@@ -93,6 +93,7 @@ struct Engine {
   DevBuf d_tables;
   DevBuf d_rmitems, d_rmrecs;   // Plan::rm_items, Plan::rm_recs (views into d_tables)
   DevBuf d_rmdir;               // Plan::rm_direct
+  DevBuf d_sm, d_phys;          // Plan::sm (codeword pairs), Plan::phys (the entries that own samples)
   const uint32_t* rm_items() const { return plan.rm_items.empty() ? nullptr : d_rmitems.as<uint32_t>(); }
   const uint4* rm_recs() const { return plan.rm_recs.empty() ? nullptr : d_rmrecs.as<uint4>(); }
   // two page-locked staging buffers used in turn, each with the event of its last DMA (waited for before it is

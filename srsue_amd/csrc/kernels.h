@@ -20,14 +20,22 @@ struct RxPlanes {
 void launch_ofdm_rx(int N, const void* iq, bool sc16, float2* grid, const MiSfDesc* sfs, const uint32_t* list,
                     uint32_t n, const float2* tw, uint32_t W, const RxPlanes& rx, hipStream_t st);
 // channel estimation (srslte_chest_dl_estimate): one workgroup per (subframe, antenna), all ports
+// list (n_list entries; nullptr = all n_sf): the subframes to estimate -- a batch with codeword pairs leaves out the
+// cw = 1 entries, whose estimates are their partners'; the metrics rows stay indexed by subframe
 void launch_chest(const float2* grid, float2* ce, const MiSfDesc* sfs, const MiCellDesc* cells,
                   const float2* crs, float* metrics, uint32_t n_sf, const RxPlanes& rx, hipStream_t st,
-                  bool compact = false /* MI_DL_FLAG_CE_COMPACT: only the 4 pilot rows per port */);
+                  bool compact = false /* MI_DL_FLAG_CE_COMPACT: only the 4 pilot rows per port */,
+                  const uint32_t* list = nullptr, uint32_t n_list = 0);
 // equalise (combining the antennas) + soft demap + descramble (srslte_predecoding_* / demod_soft / scrambling_f)
 void launch_demap(const float2* grid, const float2* ce, float* e, const MiSfDesc* sfs,
                   const MiPdschDesc* pd, const MiCellDesc* cells, const uint32_t* re_tab,
                   const uint32_t* scr, uint32_t n_sf, uint32_t max_units, float noise, const RxPlanes& rx,
                   hipStream_t st);
+// two-layer spatial multiplexing (TM3 / TM4) detection + soft demap + descramble of both codewords of every pair
+// (Plan::sm; sm_detect.hip).  Reads both antenna planes: the batch has rx.n == 2.
+void launch_sm_detect(const float2* grid, const float2* ce, float* e, const MiSmDesc* sm, uint32_t n_pairs,
+                      uint32_t max_nre, const uint32_t* re_tab, const uint32_t* scr, float noise, const RxPlanes& rx,
+                      hipStream_t st);
 // rate de-matching + HARQ combining into the group-interleaved softbuffer (srslte_rm_turbo_rx)
 void launch_rm_combine(const float* e, float* sb, const MiGroupDesc* groups, const MiLaneDesc* lanes,
                        const MiKTab* ktabs, const uint32_t* ktab_data, uint32_t n_groups,

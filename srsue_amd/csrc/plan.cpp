@@ -62,6 +62,8 @@ int Plan::build(const mi_dl_sf_cfg_t* cfgs, uint32_t n, bool with_pdsch) {
   groups.clear(); ktabs.clear(); kdata.clear(); tbs.clear(); cb_list.clear(); fft_lists.clear(); rm_items.clear(); rm_recs.clear();
   pairs.clear();
   rm_direct.clear();
+  sm.clear(); phys.clear();
+  sm_max_nre = 0;
   rm_busy = rm_dbusy = 0;
   rm_rep = false;
   fft_list_flat.clear(); fft_list_off.clear(); fft_W.clear();
@@ -75,7 +77,7 @@ int Plan::build(const mi_dl_sf_cfg_t* cfgs, uint32_t n, bool with_pdsch) {
 
   std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> cell_idx;
   std::unordered_map<ReKey, uint32_t, ReKeyHash> re_idx;        // -> offset in re_tab (this build)
-  std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>, uint32_t> scr_idx;   // (cell, rnti, sf, G) -> scr_tab
+  std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, uint32_t> scr_idx;   // (cell, rnti, sf, G, q) -> scr_tab
   std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, uint32_t> pd_idx;
   std::map<int, std::vector<uint32_t>> fft_map;
   std::vector<uint32_t> re;
@@ -98,6 +100,28 @@ int Plan::build(const mi_dl_sf_cfg_t* cfgs, uint32_t n, bool with_pdsch) {
       set_error("invalid cell configuration");
       return -1;
     }
+    // spatial multiplexing (tm 3 / 4): a pair of entries, cw 0 then cw 1, over one physical subframe (mi_dl.h)
+    const bool sm_e = c.tm == 3 || c.tm == 4;
+    if (!sm_e && (c.cw || c.pmi)) { set_error("cw and pmi must be 0 unless tm is 3 or 4"); return -1; }
+    if (sm_e) {
+      if (c.nof_ports != 2) { set_error("TM3 / TM4 need 2 ports"); return -1; }
+      if (c.cw > 1) { set_error("cw must be 0 or 1"); return -1; }
+      if (c.tm == 4 && c.pmi != 1 && c.pmi != 2) { set_error("TM4 needs pmi 1 or 2 (two layers)"); return -1; }
+      if (c.cw == 0 && (s + 1 >= n || cfgs[s + 1].cw != 1 || (cfgs[s + 1].tm != 3 && cfgs[s + 1].tm != 4))) {
+        set_error("a cw = 0 spatial multiplexing entry needs its cw = 1 partner as the next entry");
+        return -1;
+      }
+      if (c.cw == 1) {
+        const mi_dl_sf_cfg_t* p = s ? &cfgs[s - 1] : nullptr;
+        if (!p || p->cw != 0 || p->tm != c.tm || p->pmi != c.pmi || p->cell_id != c.cell_id || p->nof_prb != c.nof_prb ||
+            p->nof_ports != c.nof_ports || p->sf_idx != c.sf_idx || p->cfi != c.cfi || p->rnti != c.rnti ||
+            memcmp(p->prb_mask, c.prb_mask, sizeof(c.prb_mask))) {
+          set_error("a cw = 1 entry must follow a matching cw = 0 entry (same cell, sf_idx, cfi, tm, pmi, rnti, prb_mask)");
+          return -1;
+        }
+      }
+    }
+    const bool owns = !(sm_e && c.cw == 1);   // a cw = 1 entry owns no samples: its partner's front end serves both
     const uint32_t W = 12 * c.nof_prb;
     auto ck = std::make_tuple(c.cell_id, c.nof_prb, c.nof_ports);
     uint32_t ci;
@@ -124,14 +148,20 @@ int Plan::build(const mi_dl_sf_cfg_t* cfgs, uint32_t n, bool with_pdsch) {
     sd.cell = ci;
     sd.sf_idx = c.sf_idx;
     sd.tb = s;
-    iq_samples += (size_t)sf_len(N);
-    grid_elems += (size_t)NSYMB * W;
-    ce_elems += (size_t)NSYMB * W * c.nof_ports;
-    fft_map[N].push_back(s);
-    stage_bytes[MI_DL_STAGE_OFDM] += (double)sf_len(N) * 8 + (double)NSYMB * W * 8;
-    stage_bytes[MI_DL_STAGE_CHEST] += (double)NSYMB * W * 8 * c.nof_ports + 4.0 * W * 8;
-    bytes_compulsory += (double)sf_len(N) * 8;
-    iq_bytes += (double)sf_len(N) * 8;
+    if (owns) {
+      iq_samples += (size_t)sf_len(N);
+      grid_elems += (size_t)NSYMB * W;
+      ce_elems += (size_t)NSYMB * W * c.nof_ports;
+      fft_map[N].push_back(s);
+      stage_bytes[MI_DL_STAGE_OFDM] += (double)sf_len(N) * 8 + (double)NSYMB * W * 8;
+      stage_bytes[MI_DL_STAGE_CHEST] += (double)NSYMB * W * 8 * c.nof_ports + 4.0 * W * 8;
+      bytes_compulsory += (double)sf_len(N) * 8;
+      iq_bytes += (double)sf_len(N) * 8;
+    } else {
+      sd.iq_off = sfs[s - 1].iq_off;
+      sd.grid_off = sfs[s - 1].grid_off;
+      sd.ce_off = sfs[s - 1].ce_off;
+    }
 
     if (with_pdsch) {
       if (c.tm == 2 && c.nof_ports != 2) { set_error("TM2 needs 2 ports"); return -1; }
@@ -163,13 +193,13 @@ int Plan::build(const mi_dl_sf_cfg_t* cfgs, uint32_t n, bool with_pdsch) {
       const uint32_t nre = re_tab[re_off];
       if (c.tm == 2 && (nre & 1)) { set_error("odd RE count for SFBC"); return -1; }
       const uint32_t G = nre * c.Qm;
-      const auto sk = std::make_tuple(c.cell_id, c.rnti, c.sf_idx, G);
+      const auto sk = std::make_tuple(c.cell_id, c.rnti, c.sf_idx, G, c.cw);
       auto si = scr_idx.find(sk);
       if (si == scr_idx.end()) {
         auto& words = scr_cache[sk];
         if (words.empty()) {
           words.resize((G + 31) / 32 + 1);
-          gold_words((c.rnti << 14) | (c.sf_idx << 9) | c.cell_id, G, words.data());
+          gold_words((c.rnti << 14) | (c.cw << 13) | (c.sf_idx << 9) | c.cell_id, G, words.data());   // 36.211 6.3.1
         }
         si = scr_idx.emplace(sk, (uint32_t)scr_tab.size()).first;
         scr_tab.insert(scr_tab.end(), words.begin(), words.end());
@@ -188,8 +218,17 @@ int Plan::build(const mi_dl_sf_cfg_t* cfgs, uint32_t n, bool with_pdsch) {
       sd.pdsch = pi_;
       sd.e_off = e_floats;
       e_floats += align4(pd.G);
-      const uint32_t units = pd.tm == 2 ? pd.nre / 2 : pd.nre;
-      max_units = std::max(max_units, units);
+      if (!sm_e) {
+        const uint32_t units = pd.tm == 2 ? pd.nre / 2 : pd.nre;
+        max_units = std::max(max_units, units);
+      } else if (c.cw == 1) {
+        // the pair's detection work item: one lane per RE writes both codewords' LLRs (sm_detect.hip)
+        const MiSfDesc& s0 = sfs[s - 1];
+        const MiPdschDesc& p0 = pds[s0.pdsch];
+        sm.push_back(MiSmDesc{sd.grid_off, sd.ce_off, s0.e_off, sd.e_off, (uint32_t)NSYMB * W, pd.re_off, pd.nre,
+                              p0.scr_off, pd.scr_off, p0.Qm, pd.Qm, c.tm == 3 ? 0u : c.pmi});
+        sm_max_nre = std::max(sm_max_nre, pd.nre);
+      }
       // ---- transport block (segmentation depends on the TBS only)
       if (c.tbs != last_tbs) {
         if (cbsegm(c.tbs, &last_sg)) { set_error("segmentation failed"); return -1; }
@@ -211,13 +250,22 @@ int Plan::build(const mi_dl_sf_cfg_t* cfgs, uint32_t n, bool with_pdsch) {
         cb_eoff.push_back(eo);
         eo += E;
       }
-      stage_bytes[MI_DL_STAGE_DEMAP] += (double)pd.nre * 8 * (1 + c.nof_ports) + (double)pd.G * 4;
-      demap_in_bytes += (double)pd.nre * 8 * (1 + c.nof_ports);
+      // (a pair's grid and estimates are read once, for both codewords)
+      stage_bytes[MI_DL_STAGE_DEMAP] += (owns ? (double)pd.nre * 8 * (1 + c.nof_ports) : 0.0) + (double)pd.G * 4;
+      if (owns) demap_in_bytes += (double)pd.nre * 8 * (1 + c.nof_ports);
       bytes_compulsory += (double)c.tbs / 8;
     }
     sfs.push_back(sd);
   }
   cb_first[n] = (uint32_t)cb_E.size();
+  // with codeword pairs in the batch, channel estimation walks the entries that own samples
+  auto is_cw1 = [&](uint32_t s) { return (cfgs[s].tm == 3 || cfgs[s].tm == 4) && cfgs[s].cw == 1; };
+  for (uint32_t s = 0; s < n; s++)
+    if (is_cw1(s)) {
+      for (uint32_t t = 0; t < n; t++)
+        if (!is_cw1(t)) phys.push_back(t);
+      break;
+    }
   PLAN_T("sf");
   for (auto& kv : fft_map) {
     fft_lists.push_back(kv);
@@ -587,6 +635,8 @@ int Plan::build_codeblocks(uint32_t K, uint32_t ncb_req, bool crc24a) {
   groups.clear(); ktabs.clear(); kdata.clear(); tbs.clear(); cb_list.clear(); fft_lists.clear(); rm_items.clear(); rm_recs.clear();
   pairs.clear();
   rm_direct.clear();
+  sm.clear(); phys.clear();
+  sm_max_nre = 0;
   rm_busy = rm_dbusy = 0;
   fft_list_flat.clear(); fft_list_off.clear(); fft_W.clear();
   iq_samples = grid_elems = ce_elems = e_floats = sb_floats = scratch_floats = dec_bytes = payload_bytes = 0;

@@ -66,6 +66,14 @@ struct PlanData {
   // the IQ of bytes_compulsory, and the demap stage's grid and estimate reads
   double iq_bytes = 0, demap_in_bytes = 0;
   uint32_t cb_K = 0, cb_n = 0;
+  // spatial multiplexing (tm 3 / 4): one descriptor per cw 0 / cw 1 pair of entries -- the work list of the detection
+  // kernel (sm_detect.hip), which demap_kernel's launch skips -- and its longest RE list.  A plan that holds a pair is
+  // never fused (Engine::run) and needs two receive antennas.
+  std::vector<MiSmDesc> sm;
+  uint32_t sm_max_nre = 0;
+  // with pairs in the plan: the entries that own samples (all but the cw = 1 ones), the channel estimator's work
+  // list; empty = every entry
+  std::vector<uint32_t> phys;
 };
 
 // A PDSCH RE list depends on the cell, CFI, subframe and PRB mask only (not on RNTI, Qm or the transmission
@@ -95,7 +103,8 @@ struct Plan : PlanData {
   void build_pairs();
   // cached per-key tables (kept across rebuilds)
   std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::vector<float>> crs_cache;
-  std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t>, std::vector<uint32_t>> scr_cache;
+  // scrambling words per (cell, rnti, sf, G, codeword q)
+  std::map<std::tuple<uint32_t, uint32_t, uint32_t, uint32_t, uint32_t>, std::vector<uint32_t>> scr_cache;
   std::map<uint32_t, std::vector<std::vector<uint32_t>>> kpos_cache;   // K -> {pos, pi, crcA, crcB}
   void add_ktab(uint32_t K);   // appends K's tables to kdata and a MiKTab to ktabs
   std::map<std::pair<uint32_t, uint32_t>, std::pair<std::vector<int32_t>, uint32_t>> rank_cache;

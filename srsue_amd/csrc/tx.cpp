@@ -115,10 +115,11 @@ static void idft(std::vector<double>& a, int N) {
   }
 }
 
-int tx_subframe(const mi_dl_sf_cfg_t* c, const uint8_t* tb, const float* h, float snr_db, uint64_t seed, float* iq) {
-  const int N = symbol_sz(c->nof_prb);
-  if (N < 0 || c->tbs == 0 || c->tbs % 8 || (c->tm == 2 && c->nof_ports != 2)) return -1;
-  const uint32_t W = 12 * c->nof_prb, P = c->nof_ports, A = c->tbs, Qm = c->Qm;
+// One codeword: transport block -> CRC24A -> segmentation -> turbo code -> rate matching -> scrambling with codeword
+// index q (36.211 6.3.1), for nre REs of Qm bits on NL layers.  f: the G = nre Qm scrambled bits.
+static int encode_cw(const mi_dl_sf_cfg_t* c, const uint8_t* tb, uint32_t nre, uint32_t NL, uint32_t q,
+                     std::vector<uint8_t>& f) {
+  const uint32_t A = c->tbs, Qm = c->Qm;
   // transport block + CRC24A
   std::vector<uint8_t> b(A + 24);
   for (uint32_t i = 0; i < A; i++) b[i] = (tb[i / 8] >> (7 - i % 8)) & 1;
@@ -132,11 +133,9 @@ int tx_subframe(const mi_dl_sf_cfg_t* c, const uint8_t* tb, const float* h, floa
   }
   CbSegm sg;
   if (cbsegm(A, &sg)) return -1;
-  std::vector<uint32_t> re;
-  const uint32_t nre = pdsch_re_list(c->cell_id, c->nof_prb, P, c->cfi, c->sf_idx, c->prb_mask, re);
-  if (c->tm == 2 && (nre & 1)) return -1;
-  const uint32_t G = nre * Qm, NL = c->tm == 2 ? (c->nl_td ? c->nl_td : 2) : 1;
-  std::vector<uint8_t> f(G), cb(KMAX), d(3 * (KMAX + 4));
+  const uint32_t G = nre * Qm;
+  f.assign(G, 0);
+  std::vector<uint8_t> cb(KMAX), d(3 * (KMAX + 4));
   uint32_t pb = 0, pf = 0;
   for (uint32_t r = 0; r < sg.C; r++) {
     const uint32_t K = r < sg.Cm ? sg.Km : sg.Kp, F = r == 0 ? sg.F : 0, L = sg.C > 1 ? 24 : 0;
@@ -155,29 +154,34 @@ int tx_subframe(const mi_dl_sf_cfg_t* c, const uint8_t* tb, const float* h, floa
     pf += E;
   }
   std::vector<uint8_t> cs(G + 32);
-  gold_bits((c->rnti << 14) | (c->sf_idx << 9) | c->cell_id, G, cs.data());
+  gold_bits((c->rnti << 14) | (q << 13) | (c->sf_idx << 9) | c->cell_id, G, cs.data());
   for (uint32_t i = 0; i < G; i++) f[i] ^= cs[i];
+  return 0;
+}
 
-  std::vector<double> grid((size_t)P * NSYMB * W * 2, 0.0);
-  auto at = [&](uint32_t p, uint32_t idx) -> double* { return &grid[((size_t)p * NSYMB * W + idx) * 2]; };
-  const double s2 = 0.70710678118654752440;
-  auto put_sfbc = [&](double x0r, double x0i, double x1r, double x1i, uint32_t ia, uint32_t ib) {
+// per-port grids [P][14][W] (re, im) of doubles
+struct TxGrid {
+  std::vector<double> v;
+  uint32_t W;
+  TxGrid(uint32_t P, uint32_t W_) : v((size_t)P * NSYMB * W_ * 2, 0.0), W(W_) {}
+  double* at(uint32_t p, uint32_t idx) { return &v[((size_t)p * NSYMB * W + idx) * 2]; }
+  void put_sfbc(double x0r, double x0i, double x1r, double x1i, uint32_t ia, uint32_t ib) {
+    const double s2 = 0.70710678118654752440;
     double* y = at(0, ia); y[0] = s2 * x0r; y[1] = s2 * x0i;
     y = at(1, ia); y[0] = -s2 * x1r; y[1] = s2 * x1i;
     y = at(0, ib); y[0] = s2 * x1r; y[1] = s2 * x1i;
     y = at(1, ib); y[0] = s2 * x0r; y[1] = -s2 * x0i;
-  };
-  for (uint32_t i = 0; i < nre; i += (c->tm == 2 ? 2 : 1)) {
-    double xr, xi;
-    modulate(&f[(size_t)i * Qm], Qm, &xr, &xi);
-    if (c->tm != 2) {
-      double* y = at(0, re[i]); y[0] = xr; y[1] = xi;
-    } else {
-      double yr, yi;
-      modulate(&f[(size_t)(i + 1) * Qm], Qm, &yr, &yi);
-      put_sfbc(xr, xi, yr, yi, re[i], re[i + 1]);
-    }
   }
+};
+
+// the rest of a subframe once the PDSCH is on the grids: CRS, PCFICH, IFFT + CP, flat per-port channel, AWGN
+static void tx_finish(const mi_dl_sf_cfg_t* c, TxGrid& grid, const float* h, float snr_db, uint64_t seed, float* iq) {
+  const int N = symbol_sz(c->nof_prb);
+  const uint32_t W = grid.W, P = c->nof_ports;
+  auto at = [&](uint32_t p, uint32_t idx) -> double* { return grid.at(p, idx); };
+  auto put_sfbc = [&](double x0r, double x0i, double x1r, double x1i, uint32_t ia, uint32_t ib) {
+    grid.put_sfbc(x0r, x0i, x1r, x1i, ia, ib);
+  };
   float rs[4 * NRB_MAX];
   for (uint32_t p = 0; p < P; p++)
     for (uint32_t l = 0; l < (uint32_t)NSYMB; l++) {
@@ -248,10 +252,77 @@ int tx_subframe(const mi_dl_sf_cfg_t* c, const uint8_t* tb, const float* h, floa
     iq[2 * n] = (float)(acc[2 * n] + nr);
     iq[2 * n + 1] = (float)(acc[2 * n + 1] + ni);
   }
+}
+
+int tx_subframe(const mi_dl_sf_cfg_t* c, const uint8_t* tb, const float* h, float snr_db, uint64_t seed, float* iq) {
+  const int N = symbol_sz(c->nof_prb);
+  if (N < 0 || c->tbs == 0 || c->tbs % 8 || (c->tm == 2 && c->nof_ports != 2)) return -1;
+  const uint32_t W = 12 * c->nof_prb, P = c->nof_ports, Qm = c->Qm;
+  std::vector<uint32_t> re;
+  const uint32_t nre = pdsch_re_list(c->cell_id, c->nof_prb, P, c->cfi, c->sf_idx, c->prb_mask, re);
+  if (c->tm == 2 && (nre & 1)) return -1;
+  std::vector<uint8_t> f;
+  if (encode_cw(c, tb, nre, c->tm == 2 ? (c->nl_td ? c->nl_td : 2) : 1, 0, f)) return -1;
+  TxGrid grid(P, W);
+  for (uint32_t i = 0; i < nre; i += (c->tm == 2 ? 2 : 1)) {
+    double xr, xi;
+    modulate(&f[(size_t)i * Qm], Qm, &xr, &xi);
+    if (c->tm != 2) {
+      double* y = grid.at(0, re[i]); y[0] = xr; y[1] = xi;
+    } else {
+      double yr, yi;
+      modulate(&f[(size_t)(i + 1) * Qm], Qm, &yr, &yi);
+      grid.put_sfbc(xr, xi, yr, yi, re[i], re[i + 1]);
+    }
+  }
+  tx_finish(c, grid, h, snr_db, seed, iq);
+  return 0;
+}
+
+// Two-layer spatial multiplexing (tm 3 / 4): pair[0] / pair[1] are the cw 0 / cw 1 entries of one subframe.  Layer
+// mapping x0(i) = d0(i), x1(i) = d1(i); precoding [y0; y1] = (1/2) [[1, 1], [w, -w]] [x0; x1] at RE i of the mapping
+// order, w = (-1)^i (TM3: W D(i) U of 36.211 6.3.4.2.2), 1 or j (TM4 codebook index 1 / 2, Table 6.3.4.2.3-1).
+int tx_subframe_sm(const mi_dl_sf_cfg_t* pair, const uint8_t* tb0, const uint8_t* tb1, const float* h, float snr_db,
+                   uint64_t seed, float* iq) {
+  const mi_dl_sf_cfg_t *c0 = pair, *c1 = pair + 1;
+  const int N = symbol_sz(c0->nof_prb);
+  if (N < 0 || (c0->tm != 3 && c0->tm != 4) || c0->nof_ports != 2 || c0->cw != 0 || c1->cw != 1 || c1->tm != c0->tm ||
+      c1->pmi != c0->pmi || (c0->tm == 4 && c0->pmi != 1 && c0->pmi != 2) || c1->cell_id != c0->cell_id ||
+      c1->nof_prb != c0->nof_prb || c1->nof_ports != 2 || c1->sf_idx != c0->sf_idx || c1->cfi != c0->cfi ||
+      c1->rnti != c0->rnti || memcmp(c0->prb_mask, c1->prb_mask, sizeof(c0->prb_mask)))
+    return -1;
+  for (const mi_dl_sf_cfg_t* c : {c0, c1})
+    if (c->tbs == 0 || c->tbs % 8 || (c->Qm != 2 && c->Qm != 4 && c->Qm != 6)) return -1;
+  const uint32_t W = 12 * c0->nof_prb;
+  std::vector<uint32_t> re;
+  const uint32_t nre = pdsch_re_list(c0->cell_id, c0->nof_prb, 2, c0->cfi, c0->sf_idx, c0->prb_mask, re);
+  std::vector<uint8_t> f0, f1;
+  if (encode_cw(c0, tb0, nre, 1, 0, f0) || encode_cw(c1, tb1, nre, 1, 1, f1)) return -1;
+  TxGrid grid(2, W);
+  for (uint32_t i = 0; i < nre; i++) {
+    double ar, ai, br, bi;
+    modulate(&f0[(size_t)i * c0->Qm], c0->Qm, &ar, &ai);
+    modulate(&f1[(size_t)i * c1->Qm], c1->Qm, &br, &bi);
+    double* y = grid.at(0, re[i]);
+    y[0] = 0.5 * (ar + br);
+    y[1] = 0.5 * (ai + bi);
+    const double dr = 0.5 * (ar - br), di = 0.5 * (ai - bi);   // times w
+    y = grid.at(1, re[i]);
+    if (c0->tm == 4 && c0->pmi == 2) { y[0] = -di; y[1] = dr; }
+    else if (c0->tm == 3 && (i & 1)) { y[0] = -dr; y[1] = -di; }
+    else { y[0] = dr; y[1] = di; }
+  }
+  tx_finish(c0, grid, h, snr_db, seed, iq);
   return 0;
 }
 
 }  // namespace mi
+
+extern "C" int mi_tx_subframe_sm(const mi_dl_sf_cfg_t* cfg_pair, const uint8_t* tb0, const uint8_t* tb1,
+                                 const float* h_re_im, float snr_db, uint64_t noise_seed, float* iq) {
+  if (!cfg_pair || !tb0 || !tb1 || !iq) return -1;
+  return mi::tx_subframe_sm(cfg_pair, tb0, tb1, h_re_im, snr_db, noise_seed, iq);
+}
 
 extern "C" int mi_tx_subframe(const mi_dl_sf_cfg_t* cfg, const uint8_t* tb, const float* h_re_im, float snr_db,
                               uint64_t noise_seed, float* iq) {
