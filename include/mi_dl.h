@@ -106,7 +106,8 @@ enum { MI_DL_BUF_GRID = 0, MI_DL_BUF_CE, MI_DL_BUF_LLR, MI_DL_BUF_PAYLOAD, MI_DL
  * frequency-interpolated rows ([port][4][12 N_RB] at the subframe's ce offset) and the fused demap stage
  * interpolates each RE's estimate in time from them with the chest kernel's own expression -- identical
  * LLRs, 10 of 14 rows of channel-estimate traffic written and read never.  Batch throughput mode: the
- * batch's ce buffer then does not hold the full estimates (no MI_DL_FLAG_KEEP_LLR, no mi_dl_ctrl_* on it).
+ * batch's ce buffer then does not hold the full estimates (no MI_DL_FLAG_KEEP_LLR, no mi_dl_ctrl_* on it; mi_dl_csi_*
+ * reads either layout).
  * A run whose stage mask includes DEMAP but not CHEST after a compact estimation fails (returns -1,
  * mi_dl_last_error says why) instead of reading rows that were never written. */
 #define MI_DL_FLAG_CE_COMPACT 1024u
@@ -302,6 +303,67 @@ uint32_t      mi_dl_ctrl_n_cce(const mi_dl_ctrl_t *c, uint32_t sf);
 int           mi_dl_ctrl_llr(mi_dl_ctrl_t *c, float *host, size_t n, int upload);
 int           mi_dl_ctrl_set_phich(mi_dl_ctrl_t *c, const uint32_t *i_lowest, const uint32_t *n_dmrs);
 int           mi_dl_ctrl_phich(mi_dl_ctrl_t *c, uint32_t sf, float *soft);
+
+/* ---- CSI feedback: CQI, PMI and RI from the channel estimates -------------------
+ * What the UE reports so that an eNB can schedule TM4 with a precoder or TM3 / TM4 with two layers, computed over the
+ * channel estimates a batch's CHEST stage left in HBM (one kernel, one workgroup per physical subframe; the default
+ * batch run does not launch it).  Sample points: every subcarrier of the four CRS symbols 0, 4, 7, 11 -- the rows a
+ * MI_DL_FLAG_CE_COMPACT run keeps, so run() follows whichever layout (full or compact) the batch's last CHEST stage
+ * wrote.  Noise n of a subframe: the mean over the batch's antennas of its chest metric [3] (noise_estimate), or the
+ * value given with set_noise; either floored at 1e-9.  h_ap = antenna a's estimate of CRS port p.  Hypotheses (per-layer
+ * SINR g at a point):
+ *   MI_CSI_H_BASE      one port: sum_a |h_a0|^2 / n; two ports (transmit diversity): sum_a (|h_a0|^2 + |h_a1|^2) / (2 n)
+ *   MI_CSI_H_R1 + i    rank 1 closed loop, codebook index i = 0..3 (36.211 Table 6.3.4.2.3-1): W = (1/sqrt 2) [1, q]^T,
+ *                      q = 1, -1, j, -j;  g = sum_a |h_a0 + q h_a1|^2 / (2 n)
+ *   MI_CSI_H_R2 + 0/1  rank 2 closed loop, codebook index 1 / 2: G = H P, P = (1/2) [[1, 1], [w, -w]], w = 1 / j; per-layer
+ *                      MMSE SINR g_l = 1 / [(I + G^H G / n)^-1]_ll - 1
+ *   MI_CSI_H_CDD       rank 2 open loop (TM3, w alternating +1 / -1): both layers (cap[R2 + 0][0] + cap[R2 + 0][1]) / 2
+ * cap[band][h][layer] = mean over the band's points of log2(1 + g) (rank-1 hypotheses: layer 0 only); band 0 = the whole
+ * bandwidth, bands 1..n_sb = the higher-layer-configured subbands of 36.213 Table 7.2.1-3 (mi_csi_subbands: 4 / 6 / 8 PRB
+ * for 8..26 / 27..63 / 64..110 PRB, none below 8, the last subband takes the remaining PRBs).  cqi[band][h][layer] =
+ * srslte_cqi_from_snr(10 log10(2^cap - 1)).  Decisions, from the wideband capacities, ties to the lower index:
+ * pmi_r1 = argmax_i cap[0][R1 + i][0]; cb_r2 = 1 or 2 = argmax of the two layers' sum; ri_cl = 2 if that sum exceeds
+ * the best rank-1 capacity, else 1; ri_ol = 2 if 2 cap[0][CDD][0] > cap[0][BASE][0], else 1.  Evaluated (valid_mask bit
+ * h; the other cells are 0, the decisions of missing hypotheses 0 / rank 1): one port: BASE; two ports, one antenna:
+ * BASE and R1; two ports, two antennas: all.
+ * The object describes the plan its batch held at create(), like mi_dl_ctrl_*: after mi_dl_batch_replan create a new
+ * one (run() returns -1 when the batch's layout no longer matches).  The cw = 1 entry of a spatial multiplexing pair
+ * reports its partner's record.  On a two-antenna batch CSI combines both planes.
+ * run(): asynchronous, on `stream`; the caller orders it after the batch's CHEST stage (same stream, or an event) and
+ * before the batch's next run.  -1 before any CHEST stage (or MI_DL_BUF_CE upload) of the batch.  set_noise(): one
+ * value per batch entry (copied; synchronises), NULL = the chest metrics again (the default).  result() / download()
+ * synchronise run()'s stream; download() copies all mi_dl_csi_n(c) records.  device_ptr(): the records in HBM.
+ * mi_csi_pack_pucch: the PUCCH format 2 payload for 2 ports (36.212 Tables 5.2.3.3.1-1 / -2), bits MSB first, one per
+ * byte (as srslte_cqi_value_pack; fits MI_PUCCH_UCI and mi_ul_cfg_t.cqi): tm 1 / 2 / 3: the 4-bit wideband CQI of
+ * BASE (of CDD when tm 3 and ri_ol = 2); tm 4, ri_cl = 1: CQI (4) + PMI (2) = 6 bits; tm 4, ri_cl = 2: codeword 0's
+ * CQI (4) + spatial differential CQI (3, 36.213 Table 7.2-2: offset = CQI0 - CQI1; 0, 1, 2, >= 3 -> 0, 1, 2, 3 and
+ * <= -4, -3, -2, -1 -> 4, 5, 6, 7) + PMI (1 = cb_r2 - 1) = 8 bits.  Returns the bit count (*ri = the rank reported
+ * with it), -1 on a bad argument or a report whose hypotheses the record does not hold. */
+#define MI_CSI_NHYP   8
+#define MI_CSI_MAX_SB 14
+enum { MI_CSI_H_BASE = 0, MI_CSI_H_R1 = 1, MI_CSI_H_CDD = 5, MI_CSI_H_R2 = 6 };
+typedef struct {
+  uint32_t valid_mask;          /* bit h: hypothesis h was evaluated */
+  uint32_t n_sb, sb_prb;        /* subbands and their size in PRB (0, 0: none) */
+  uint32_t pmi_r1;              /* best rank-1 codebook index 0..3 */
+  uint32_t cb_r2;               /* best rank-2 codebook index 1 or 2 (0: not evaluated) */
+  uint32_t ri_cl, ri_ol;        /* rank 1 or 2, closed loop (TM4) and open loop (TM3) */
+  float    noise;               /* the n used */
+  float    cap[1 + MI_CSI_MAX_SB][MI_CSI_NHYP][2];
+  uint8_t  cqi[1 + MI_CSI_MAX_SB][MI_CSI_NHYP][2];
+} mi_dl_csi_result_t;
+typedef struct mi_dl_csi mi_dl_csi_t;
+mi_dl_csi_t *mi_dl_csi_create(mi_dl_batch_t *b);
+void         mi_dl_csi_destroy(mi_dl_csi_t *c);
+uint32_t     mi_dl_csi_n(const mi_dl_csi_t *c);   /* records = entries of the batch */
+int          mi_dl_csi_set_noise(mi_dl_csi_t *c, const float *per_sf_or_NULL);
+int          mi_dl_csi_run(mi_dl_csi_t *c, void *stream);
+int          mi_dl_csi_result(mi_dl_csi_t *c, uint32_t sf, mi_dl_csi_result_t *out);
+int          mi_dl_csi_download(mi_dl_csi_t *c, mi_dl_csi_result_t *out /* mi_dl_csi_n(c) */);
+void        *mi_dl_csi_device_ptr(mi_dl_csi_t *c);
+/* host only */
+int          mi_csi_subbands(uint32_t nof_prb, uint32_t *sb_prb, uint32_t *n_sb);   /* -1: nof_prb outside 6..110 */
+int          mi_csi_pack_pucch(uint32_t tm, const mi_dl_csi_result_t *r, uint8_t bits[11], uint32_t *ri);
 
 /* ---- sync front end ----------------------------------------------------
  * The data-parallel part of srslte_ue_sync_zerocopy (phch_recv.cc:321): PSS timing + N_ID_2 search,

@@ -216,10 +216,21 @@ def lib():
             "mi_ul_pusch_power": (C.c_float, [vp, C.c_float, C.c_float, u32, u32]),
             "mi_ul_pucch_power": (C.c_float, [vp, C.c_float, u32, u32, u32]),
             "mi_ul_srs_power": (C.c_float, [vp, C.c_float, u32]),
+            "mi_dl_csi_create": (vp, [vp]),
+            "mi_dl_csi_destroy": (None, [vp]),
+            "mi_dl_csi_n": (u32, [vp]),
+            "mi_dl_csi_set_noise": (C.c_int, [vp, vp]),
+            "mi_dl_csi_run": (C.c_int, [vp, vp]),
+            "mi_dl_csi_result": (C.c_int, [vp, u32, vp]),
+            "mi_dl_csi_download": (C.c_int, [vp, vp]),
+            "mi_dl_csi_device_ptr": (vp, [vp]),
+            "mi_csi_subbands": (C.c_int, [u32, vp, vp]),
+            "mi_csi_pack_pucch": (C.c_int, [u32, vp, vp, vp]),
         }
-        # the receive-diversity entry points are absent from a library built before them, which an A/B run selects
+        # the receive-diversity and CSI entry points are absent from a library built before them, which an A/B run selects
         # with SRSUE_AMD_LIB (tools/ab_libs.sh): such a library binds without them, and calling one raises
-        rx_names = {n for n in sig if n.endswith("_rx") or "_rx_" in n or n in ("mi_dl_batch_n_rx", "mi_tx_subframe_sm")}
+        rx_names = {n for n in sig if n.endswith("_rx") or "_rx_" in n or "_csi_" in n or
+                    n in ("mi_dl_batch_n_rx", "mi_tx_subframe_sm")}
         for name, (res, args) in sig.items():
             if name in rx_names and "SRSUE_AMD_LIB" in os.environ and not hasattr(L, name):
                 continue
@@ -255,6 +266,8 @@ def emu():
         E.emu_last_error.argtypes = []
         E.emu_pdsch_llr_sm.restype = C.c_int
         E.emu_pdsch_llr_sm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        E.emu_csi.restype = C.c_int
+        E.emu_csi.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
         _emu = E
     return _emu
 
@@ -571,6 +584,112 @@ class Ctrl:
     def close(self):
         if self.h:
             lib().mi_dl_ctrl_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+CSI_NHYP, CSI_MAX_SB = 8, 14
+CSI_H_BASE, CSI_H_R1, CSI_H_CDD, CSI_H_R2 = 0, 1, 5, 6
+
+
+class CsiResult(C.Structure):
+    """mi_dl_csi_result_t: cap / cqi are [band][hypothesis][layer], band 0 = the whole bandwidth"""
+    _fields_ = [(n, C.c_uint32) for n in ("valid_mask", "n_sb", "sb_prb", "pmi_r1", "cb_r2", "ri_cl", "ri_ol")] + \
+               [("noise", C.c_float), ("cap", C.c_float * 2 * CSI_NHYP * (1 + CSI_MAX_SB)),
+                ("cqi", C.c_uint8 * 2 * CSI_NHYP * (1 + CSI_MAX_SB))]
+
+    def cap_array(self):
+        return np.ctypeslib.as_array(self.cap).copy()
+
+    def cqi_array(self):
+        return np.ctypeslib.as_array(self.cqi).copy()
+
+
+def csi_subbands(nof_prb):
+    """(subband size in PRB, number of subbands) of 36.213 Table 7.2.1-3 (mi_csi_subbands); (0, 0) = none"""
+    k, n = C.c_uint32(), C.c_uint32()
+    if lib().mi_csi_subbands(nof_prb, C.byref(k), C.byref(n)):
+        raise ValueError("mi_csi_subbands: " + last_error())
+    return k.value, n.value
+
+
+def csi_pack_pucch(tm, res):
+    """(bits MSB first, rank) of the PUCCH format 2 CQI / PMI report of a CsiResult (mi_csi_pack_pucch)"""
+    bits = np.zeros(11, np.uint8)
+    ri = C.c_uint32()
+    n = lib().mi_csi_pack_pucch(tm, C.byref(res), bits.ctypes.data, C.byref(ri))
+    if n < 0:
+        raise ValueError("mi_csi_pack_pucch: " + last_error())
+    return bits[:n].copy(), ri.value
+
+
+def emu_csi(nof_prb, ports, n_rx, ces, noise, compact=False):
+    """TEST-ONLY: the CSI record of one subframe from the host emulation of csi_kernel; ces [n_rx][ports][14 or 4]
+    [12 nof_prb], complex or interleaved float32"""
+    a = np.asarray(ces)
+    a = np.ascontiguousarray(a, np.complex64) if np.iscomplexobj(a) else np.ascontiguousarray(a, np.float32).view(np.complex64)
+    if a.size != n_rx * ports * (4 if compact else 14) * 12 * nof_prb:
+        raise ValueError("emu_csi: estimates do not match the configuration")
+    r = CsiResult()
+    if emu().emu_csi(nof_prb, ports, n_rx, int(compact), a.ctypes.data, float(noise), C.byref(r)):
+        raise ValueError("emu_csi: bad configuration")
+    return r
+
+
+class Csi:
+    """CSI feedback (CQI / PMI / RI) over a batch's channel estimates (mi_dl_csi_*); describes the plan the batch
+    held when it was created."""
+
+    def __init__(self, batch):
+        self.batch = batch
+        self.h = lib().mi_dl_csi_create(batch.h)
+        if not self.h:
+            raise RuntimeError("mi_dl_csi_create: " + last_error())
+
+    @property
+    def n(self):
+        return lib().mi_dl_csi_n(self.h)
+
+    def set_noise(self, per_sf=None):
+        """one noise value per batch entry, or None = the chest metrics (the default)"""
+        if per_sf is None:
+            rc = lib().mi_dl_csi_set_noise(self.h, None)
+        else:
+            a = np.ascontiguousarray(per_sf, np.float32)
+            if a.size != self.n:
+                raise ValueError("set_noise: one value per batch entry")
+            rc = lib().mi_dl_csi_set_noise(self.h, a.ctypes.data)
+        if rc:
+            raise RuntimeError("mi_dl_csi_set_noise: " + last_error())
+
+    def run(self, stream_ptr=None):
+        if lib().mi_dl_csi_run(self.h, C.c_void_p(stream_ptr or 0)):
+            raise RuntimeError("mi_dl_csi_run: " + last_error())
+
+    def result(self, sf):
+        r = CsiResult()
+        if lib().mi_dl_csi_result(self.h, sf, C.byref(r)):
+            raise RuntimeError("mi_dl_csi_result: " + last_error())
+        return r
+
+    def download(self):
+        """every entry's record (a ctypes array of CsiResult)"""
+        arr = (CsiResult * self.n)()
+        if lib().mi_dl_csi_download(self.h, C.cast(arr, C.c_void_p)):
+            raise RuntimeError("mi_dl_csi_download: " + last_error())
+        return arr
+
+    def device_ptr(self):
+        return lib().mi_dl_csi_device_ptr(self.h)
+
+    def close(self):
+        if self.h:
+            lib().mi_dl_csi_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -126,7 +126,10 @@ int mi_dl_batch_upload(mi_dl_batch_t* b, int which, const void* host, size_t byt
   mi::DevBuf* d = buf_of(b, which, &n);
   if (!d || bytes > n) { mi::set_error("bad buffer or size"); return -1; }
   if (!mi::hip_ok(hipStreamSynchronize(b->eng.last_stream), "sync")) return -1;
-  return mi::hip_ok(hipMemcpy(d->p, host, bytes, hipMemcpyHostToDevice), "upload") ? 0 : -1;
+  if (!mi::hip_ok(hipMemcpy(d->p, host, bytes, hipMemcpyHostToDevice), "upload")) return -1;
+  if (which == MI_DL_BUF_CE) b->eng.ce_written = true;
+  if (which == MI_DL_BUF_METRICS) b->eng.metrics_written = true;
+  return 0;
 }
 
 int mi_dl_batch_download(mi_dl_batch_t* b, int which, void* host, size_t bytes) {

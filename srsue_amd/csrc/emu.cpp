@@ -12,6 +12,7 @@
 
 #include <vector>
 
+#include "csi_body.h"
 #include "demap_body.h"
 #include "kernels_consts.h"
 #include "plan.h"
@@ -423,6 +424,41 @@ extern "C" int emu_pdsch_llr_sm(const mi_dl_sf_cfg_t* cfg_pair, const float* gri
   memcpy(out0, &e[d.e0], (size_t)d.nre * d.qm0 * sizeof(float));
   memcpy(out1, &e[d.e1], (size_t)d.nre * d.qm1 * sizeof(float));
   return (int)d.nre;
+}
+
+// The CSI record of one subframe (csi_body.h: the arithmetic of csi_kernel, point by point) from its channel estimates
+// ces ([n_rx][ports][rows][W] float2, rows = 14, or 4 when compact: the pilot rows only) and noise n.  Returns 0, -1 on a
+// bad port / antenna count or bandwidth.
+extern "C" int emu_csi(uint32_t nof_prb, uint32_t ports, uint32_t n_rx, int compact, const float* ces, float noise,
+                       mi_dl_csi_result_t* out) {
+  MiCsiSf d{};
+  if (ports < 1 || ports > 2 || n_rx < 1 || n_rx > 2 || !mi::csi_subbands(nof_prb, &d.sb_prb, &d.n_sb)) return -1;
+  d.W = 12 * nof_prb;
+  d.ports = ports;
+  const uint32_t mask = mi::csi_valid_mask(ports, n_rx), rows = compact ? 4 : mi::NSYMB;
+  const size_t port = (size_t)rows * d.W, c_rx = port * ports;
+  const float2* c = reinterpret_cast<const float2*>(ces);
+  const float2 zero = make_float2(0.f, 0.f);
+  noise = fmaxf(noise, 1e-9f);
+  const float inv_n = 1.0f / noise;
+  float sums[1 + MI_CSI_MAX_SB][mi::CSI_NACC] = {};
+  const uint32_t n_chunk = d.n_sb ? d.n_sb : 1u, cw = d.n_sb ? 12u * d.sb_prb : d.W;
+  for (uint32_t ch = 0; ch < n_chunk; ch++) {
+    const uint32_t k0 = ch * cw, k1 = ch + 1 == n_chunk ? d.W : k0 + cw;
+    for (int r = 0; r < 4; r++) {
+      float acc[mi::CSI_NACC] = {};
+      const float2* c00 = c + (size_t)(compact ? r : mi::CE_PL[r]) * d.W;
+      for (uint32_t k = k0; k < k1; k++)
+        mi::csi_point(c00[k], ports == 2 ? c00[port + k] : zero, n_rx == 2 ? c00[c_rx + k] : zero,
+                      ports == 2 && n_rx == 2 ? c00[c_rx + port + k] : zero, mask, inv_n, acc);
+      for (int i = 0; i < mi::CSI_NACC; i++) sums[1 + ch][i] += acc[i];
+    }
+    for (int i = 0; i < mi::CSI_NACC; i++) sums[0][i] += sums[1 + ch][i];
+  }
+  memset(out, 0, sizeof(*out));
+  for (uint32_t t = 0; t < (uint32_t)mi::CSI_CELLS; t++) mi::csi_cell(t, sums, d, mask, out);
+  mi::csi_decide(sums[0], d, mask, noise, out);
+  return 0;
 }
 
 // The packed decoder's trellis start (tdec_p2_body.h header, p2.h tadd_a): the LLRs of steps 0..2 taken from the start

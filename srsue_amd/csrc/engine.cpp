@@ -357,7 +357,10 @@ int Engine::run(const void* d_iq, hipStream_t st, uint32_t mask, float* sb_overr
     launch_chest(d_grid.as<float2>(), d_ce.as<float2>(), d_sfs.as<MiSfDesc>(), d_cells.as<MiCellDesc>(),
                  d_crs.as<float2>(), d_metrics.as<float>(), nsf, rx, st, compact,
                  P.phys.empty() ? nullptr : d_phys.as<uint32_t>(), (uint32_t)P.phys.size());
-  if (mask & (1u << MI_DL_STAGE_CHEST)) ce_compact = compact;
+  if (mask & (1u << MI_DL_STAGE_CHEST)) {
+    ce_compact = compact;
+    ce_written = metrics_written = true;
+  }
   mark(2);
   if (P.has_pdsch) {
     float* sb = sb_override ? sb_override : d_sb.as<float>();

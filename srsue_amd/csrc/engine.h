@@ -126,6 +126,9 @@ struct Engine {
   // layout the last channel-estimation stage wrote: true = compact (4 pilot rows per port).  A run that
   // reads the estimates without re-estimating them is rejected while they are compact
   bool ce_compact = false;
+  // the estimates / the metrics hold something: a CHEST stage ran (both) or MI_DL_BUF_CE / _METRICS was uploaded.  What
+  // reads them outside a run (mi_dl_csi_run) refuses until then
+  bool ce_written = false, metrics_written = false;
   // profiling: one event set per run since the last reset (MI_DL_FLAG_PROFILE)
   std::vector<std::vector<hipEvent_t>> ev_sets;
   size_t ev_used = 0;

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "srslte/srslte.h"
+#include "cqi_table.h"
 #include "srs.h"
 
 namespace mi {
@@ -87,13 +88,7 @@ int srslte_refsignal_srs_send_ue(uint32_t I, uint32_t tti) {
 
 // wideband CQI from the reference-signal SNR (dB): the SNR thresholds of CQI 1..15 srsLTE 1.0 used for
 // its periodic reports (SURVEY.md [X]: recollection, srsLTE is not in the container)
-uint8_t srslte_cqi_from_snr(float snr) {
-  static const float thr[15] = {1.95f, 4.0f, 6.0f, 8.0f, 10.0f, 11.95f, 14.05f, 16.0f,
-                                17.9f, 19.9f, 21.5f, 23.45f, 25.0f, 27.3f, 29.0f};
-  for (int c = 14; c >= 0; c--)
-    if (snr >= thr[c]) return (uint8_t)(c + 1);
-  return 0;
-}
+uint8_t srslte_cqi_from_snr(float snr) { return mi::cqi_from_snr_db(snr); }   // the table: cqi_table.h
 
 // 36.212 5.2.3.3.1: wideband CQI = 4 bits; UE-selected subband CQI = 4 bits + the subband label (L = 1
 // bit here, srsLTE 1.0's packing [X]); bits MSB first, one per byte; returns the bit count
