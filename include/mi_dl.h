@@ -135,8 +135,8 @@ mi_dl_batch_t *mi_dl_batch_create(const mi_dl_sf_cfg_t *cfgs, uint32_t n_sf, uin
  * onto the planes directly.  mi_dl_batch_iq_samples stays one plane's samples; the d_iq of a run holds n_rx planes;
  * mi_dl_batch_bytes / _upload / _download / _device_ptr cover all planes.  The strides follow a re-plan.
  * MI_DL_FLAG_IQ_SC16, MI_DL_FLAG_CE_COMPACT and MI_DL_FLAG_KEEP_LLR work as with one antenna (the LLR stream is the
- * combined one).  mi_dl_ctrl_* and mi_pbch_* on a two-antenna batch read antenna 0 (plane 0): the control channels
- * are not combined.  The per-TTI srslte_ue_dl_* API stays single-antenna.
+ * combined one).  mi_pbch_* and mi_dl_ctrl_create on a two-antenna batch read antenna 0 (plane 0); a control object
+ * created with MI_CTRL_FLAG_RX_COMBINE combines both planes.  The per-TTI srslte_ue_dl_* API stays single-antenna.
  * Spatial multiplexing (tm 3 / 4 entry pairs, mi_dl_sf_cfg_t): only on a batch, pipe or re-plan with n_rx = 2 (else
  * NULL / -1 and mi_last_error).  The pair's two layers are detected per RE over both antennas,
  *   x^ = (G^H G + noise I)^-1 G^H y,  G = H P_i,  H[a][p] = antenna a's estimate of port p,  noise = 0.01,
@@ -285,12 +285,31 @@ int    mi_pdsch_G(const mi_dl_sf_cfg_t *cfg);
  * 1 PCFICH, 2 PDCCH soft bits, 4 blind search, 8 PHICH); result() returns the first DCI of the
  * subframe in srsLTE's search order (one DCI size over all candidates of a space at a time): `ul` 0 =
  * DL for a C-RNTI (UE-specific L = 1, 2, 4, 8 with 1A then 1, common L = 4, 8 with 1A), 1 = UL format 0,
- * 2 = DL for an SI/RA/P-RNTI (common space only, 1A then 1C).  format: 0 = 0, 1 = 1, 2 = 1A, 3 = 1C.
+ * 2 = DL for an SI/RA/P-RNTI (common space only, 1A then 1C).  format: 0 = 0, 1 = 1, 2 = 1A, 3 = 1C (4 = 2, 5 = 2A
+ * with MI_CTRL_FLAG_TM_FORMATS, below).
  * Returns 1 found, 0 not found, -1 error.  PHICH (srslte_ue_dl_decode_phich, phch_worker.cc:381): set_phich() sets per subframe the
  * UL grant's lowest PRB index and DMRS cyclic shift (36.213 9.1.2; default 0, 0), phich() returns the
- * HARQ indicator (1 ACK, 0 NACK, -1 error) and its soft value (> 0 favours ACK). */
+ * HARQ indicator (1 ACK, 0 NACK, -1 error) and its soft value (> 0 favours ACK).
+ *
+ * mi_dl_ctrl_create_flags (flags = 0 is mi_dl_ctrl_create):
+ *   MI_CTRL_FLAG_RX_COMBINE  two-antenna batch only (else NULL and mi_last_error): PCFICH, the PDCCH soft bits and PHICH
+ *     combine both antenna planes per RE with the PDSCH demapper's maximum-ratio combining (mi_dl_batch_create_rx): one
+ *     port x = sum_a y_a h_a* / (sum_a |h_a|^2 + noise); two ports the SFBC numerators and |h00|^2 + |h11|^2 summed over
+ *     the antennas (the one-port PHICH floors the summed denominator at 1e-9).  The blind search reads the combined
+ *     soft bits.  Without the flag a two-antenna batch's control object reads plane 0, as before.
+ *   MI_CTRL_FLAG_TM_FORMATS  the second DCI size of the UE-specific space follows the entry's tm: tm 1 / 2 format 1, tm 3
+ *     format 2A, tm 4 format 2 (2 CRS ports; 36.212 5.3.3.1.5 / 5.3.3.1.5A), so the search order for ul = 0 is the 1A
+ *     size, then that format, then the common space's 1A size, and the job count per subframe does not grow.  result()
+ *     reports format 4 = format 2 and 5 = format 2A (unpack with mi_dci_dl2_unpack).  The cw = 1 entry of a codeword pair
+ *     owns no samples: it gets no jobs, and result / n_cce / llr_offset / phich on it report its partner's.  Without the
+ *     flag a pair's two entries are searched as two format 1 subframes, as before.
+ * mi_dl_ctrl_n_jobs: the (candidate, size) decodes of one run. */
+#define MI_CTRL_FLAG_RX_COMBINE 1u
+#define MI_CTRL_FLAG_TM_FORMATS 2u
 typedef struct mi_dl_ctrl mi_dl_ctrl_t;
 mi_dl_ctrl_t *mi_dl_ctrl_create(mi_dl_batch_t *b, uint32_t phich_ng);
+mi_dl_ctrl_t *mi_dl_ctrl_create_flags(mi_dl_batch_t *b, uint32_t phich_ng, uint32_t flags);
+uint32_t      mi_dl_ctrl_n_jobs(const mi_dl_ctrl_t *c);
 void          mi_dl_ctrl_destroy(mi_dl_ctrl_t *c);
 int           mi_dl_ctrl_run(mi_dl_ctrl_t *c, void *stream);
 int           mi_dl_ctrl_run_stages(mi_dl_ctrl_t *c, uint32_t mask, void *stream);
@@ -303,6 +322,39 @@ uint32_t      mi_dl_ctrl_n_cce(const mi_dl_ctrl_t *c, uint32_t sf);
 int           mi_dl_ctrl_llr(mi_dl_ctrl_t *c, float *host, size_t n, int upload);
 int           mi_dl_ctrl_set_phich(mi_dl_ctrl_t *c, const uint32_t *i_lowest, const uint32_t *n_dmrs);
 int           mi_dl_ctrl_phich(mi_dl_ctrl_t *c, uint32_t sf, float *soft);
+
+/* ---- DCI formats 2 / 2A: the grants of TM4 / TM3 (36.212 5.3.3.1.5 / 5.3.3.1.5A; host only, no device) ----------
+ * FDD, 2 CRS ports (any other port count is rejected: -1 and mi_last_error).  Field order: [resource allocation header
+ * if N_RB > 10], ceil(N_RB / P) resource-block assignment bits (type 0: RBG bitmap; type 1: subset, shift, bitmap:
+ * 36.213 7.1.6.1 / 7.1.6.2), TPC 2, HARQ process 3, TB-to-codeword swap 1, TB 1 (MCS 5, NDI 1, RV 2), TB 2 likewise,
+ * precoding information 3 (format 2) / 0 (format 2A); one zero bit appended when the size is one of Table 5.3.3.1.2-1.
+ * Sizes at 6 / 15 / 25 / 50 / 75 / 100 PRB: format 2: 31 34 39 43 45 51; format 2A: 28 31 36 41 42 48.  Bits are one per
+ * byte, as mi_dl_ctrl_result returns them.
+ * mi_dci_dl2_to_cfg turns an unpacked grant into the batch entries that decode it.  base: cell_id, nof_prb, nof_ports,
+ * sf_idx, cfi and rnti of the subframe.  new_tb[t]: the caller's HARQ entity's verdict on TB t's NDI (MAC is out of
+ * scope).  reported_cb_r2: the rank-2 codebook index the UE last reported (mi_dl_csi_result_t.cb_r2), used when the
+ * precoding information says "as reported".  prb_mask from the type 0 / type 1 assignment; per enabled TB, tbs / Qm from
+ * the MCS at the allocation's PRB count (one layer per codeword), rv from the DCI.  TB-to-codeword mapping of Tables
+ * 5.3.3.1.5-1 / -2: the swap flag with both TBs enabled, a single enabled TB on codeword 0.  Both TBs enabled: format 2A
+ * a tm = 3 pair; format 2 a tm = 4 pair with pmi 1 / 2 for pinfo 0 / 1, pmi = reported_cb_r2 for pinfo 2 (-1 unless that
+ * is 1 or 2), -1 for pinfo 3..7.  One TB enabled: format 2A, or format 2 with pinfo 0 (transmit diversity): one tm = 2
+ * entry (nl_td = 2, cw = pmi = 0); format 2 with pinfo 1..6 (rank-1 closed-loop precoding, not built): -1.  MCS 29..31:
+ * -1.  Writes 1 or 2 entries and returns that number; every -1 leaves out untouched. */
+enum { MI_DCI_2 = 4, MI_DCI_2A = 5 };
+typedef struct {
+  uint32_t format, alloc_type;                 /* alloc_type 0 / 1 (36.213 7.1.6.1 / 7.1.6.2) */
+  uint32_t type0_alloc;                        /* RBG bitmap, MSB = RBG 0 */
+  uint32_t type1_subset, type1_shift, type1_bitmap;
+  uint32_t tpc_pucch, harq_process, tb_cw_swap;
+  struct { uint32_t mcs, ndi, rv, enabled; } tb[2];   /* enabled = !(mcs == 0 && rv == 1) */
+  uint32_t pinfo;                              /* format 2: the 3 precoding-information bits; 2A with 2 ports: 0 */
+} mi_dci_dl2_t;
+int mi_dci_dl2_size(uint32_t format, uint32_t nof_prb, uint32_t nof_ports);          /* bits, -1 */
+int mi_dci_dl2_pack(uint32_t nof_prb, uint32_t nof_ports, const mi_dci_dl2_t *d, uint8_t bits[64]);   /* bit count, -1 */
+int mi_dci_dl2_unpack(uint32_t format, uint32_t nof_prb, uint32_t nof_ports, const uint8_t *bits, uint32_t nbits,
+                      mi_dci_dl2_t *d);                                               /* 0, -1 */
+int mi_dci_dl2_to_cfg(const mi_dci_dl2_t *d, const mi_dl_sf_cfg_t *base, const uint8_t new_tb[2],
+                      uint32_t reported_cb_r2, mi_dl_sf_cfg_t out[2]);
 
 /* ---- CSI feedback: CQI, PMI and RI from the channel estimates -------------------
  * What the UE reports so that an eNB can schedule TM4 with a precoder or TM3 / TM4 with two layers, computed over the

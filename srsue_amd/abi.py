@@ -122,6 +122,12 @@ def lib():
             "mi_sf_len": (C.c_int, [u32]),
             "mi_pdsch_G": (C.c_int, [vp]),
             "mi_dl_ctrl_create": (vp, [vp, u32]),
+            "mi_dl_ctrl_create_flags": (vp, [vp, u32, u32]),
+            "mi_dl_ctrl_n_jobs": (u32, [vp]),
+            "mi_dci_dl2_size": (C.c_int, [u32, u32, u32]),
+            "mi_dci_dl2_pack": (C.c_int, [u32, u32, vp, vp]),
+            "mi_dci_dl2_unpack": (C.c_int, [u32, u32, u32, vp, u32, vp]),
+            "mi_dci_dl2_to_cfg": (C.c_int, [vp, vp, vp, u32, vp]),
             "mi_dl_ctrl_destroy": (None, [vp]),
             "mi_dl_ctrl_run": (C.c_int, [vp, vp]),
             "mi_dl_ctrl_run_stages": (C.c_int, [vp, u32, vp]),
@@ -227,10 +233,10 @@ def lib():
             "mi_csi_subbands": (C.c_int, [u32, vp, vp]),
             "mi_csi_pack_pucch": (C.c_int, [u32, vp, vp, vp]),
         }
-        # the receive-diversity and CSI entry points are absent from a library built before them, which an A/B run selects
-        # with SRSUE_AMD_LIB (tools/ab_libs.sh): such a library binds without them, and calling one raises
-        rx_names = {n for n in sig if n.endswith("_rx") or "_rx_" in n or "_csi_" in n or
-                    n in ("mi_dl_batch_n_rx", "mi_tx_subframe_sm")}
+        # the receive-diversity, CSI and format 2 / 2A entry points are absent from a library built before them, which an
+        # A/B run selects with SRSUE_AMD_LIB (tools/ab_libs.sh): such a library binds without them, and calling one raises
+        rx_names = {n for n in sig if n.endswith("_rx") or "_rx_" in n or "_csi_" in n or "_dci_dl2_" in n or
+                    n in ("mi_dl_batch_n_rx", "mi_tx_subframe_sm", "mi_dl_ctrl_create_flags", "mi_dl_ctrl_n_jobs")}
         for name, (res, args) in sig.items():
             if name in rx_names and "SRSUE_AMD_LIB" in os.environ and not hasattr(L, name):
                 continue
@@ -268,6 +274,8 @@ def emu():
         E.emu_pdsch_llr_sm.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         E.emu_csi.restype = C.c_int
         E.emu_csi.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_float, C.c_void_p]
+        E.emu_pdcch_llr_rx.restype = C.c_int
+        E.emu_pdcch_llr_rx.argtypes = [C.c_uint32] * 7 + [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
         _emu = E
     return _emu
 
@@ -527,12 +535,23 @@ class Plan:
 class Ctrl:
     """DL control channels over a batch's grid / channel estimates (mi_dl_ctrl_*)."""
     PCFICH, LLR, SEARCH, PHICH = 1, 2, 4, 8
+    FLAG_RX_COMBINE, FLAG_TM_FORMATS = 1, 2
 
-    def __init__(self, batch, phich_ng=2):
+    def __init__(self, batch, phich_ng=2, combine=False, tm_formats=False):
+        """combine: a two-antenna batch's PCFICH, PDCCH soft bits and PHICH combine both planes (else plane 0 alone);
+        tm_formats: the UE-specific space's second DCI size follows the entry's tm (format 2A for tm 3, 2 for tm 4) and
+        the cw = 1 entry of a pair reports its partner's results (mi_dl_ctrl_create_flags)."""
         self.batch = batch
-        self.h = lib().mi_dl_ctrl_create(batch.h, phich_ng)
+        flags = (self.FLAG_RX_COMBINE if combine else 0) | (self.FLAG_TM_FORMATS if tm_formats else 0)
+        self.h = lib().mi_dl_ctrl_create_flags(batch.h, phich_ng, flags) if flags else \
+            lib().mi_dl_ctrl_create(batch.h, phich_ng)
         if not self.h:
             raise RuntimeError("mi_dl_ctrl_create: " + last_error())
+
+    @property
+    def n_jobs(self):
+        """(candidate, DCI size) decodes of one run"""
+        return lib().mi_dl_ctrl_n_jobs(self.h)
 
     def set_phich(self, i_lowest, n_dmrs):
         """per-subframe PHICH queries: the UL grant's lowest PRB index and DMRS cyclic shift"""
@@ -591,6 +610,90 @@ class Ctrl:
             self.close()
         except Exception:
             pass
+
+
+DCI_2, DCI_2A = 4, 5
+
+
+class _Dci2Tb(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("mcs", "ndi", "rv", "enabled")]
+
+
+class Dci2(C.Structure):
+    """mi_dci_dl2_t: an unpacked DCI format 2 / 2A (36.212 5.3.3.1.5 / 5.3.3.1.5A)"""
+    _fields_ = [(n, C.c_uint32) for n in ("format", "alloc_type", "type0_alloc", "type1_subset", "type1_shift",
+                                          "type1_bitmap", "tpc_pucch", "harq_process", "tb_cw_swap")] + \
+               [("tb", _Dci2Tb * 2), ("pinfo", C.c_uint32)]
+
+    def as_tuple(self):
+        return tuple(getattr(self, n) for n, _ in self._fields_[:9]) + \
+            tuple((t.mcs, t.ndi, t.rv, t.enabled) for t in self.tb) + (self.pinfo,)
+
+
+def dci2(format=DCI_2, alloc_type=0, type0_alloc=0, type1_subset=0, type1_shift=0, type1_bitmap=0, tpc_pucch=0,
+         harq_process=0, tb_cw_swap=0, tb=((0, 0, 0), (0, 0, 0)), pinfo=0):
+    """tb: (mcs, ndi, rv) of TB 1 and TB 2; a TB is disabled by mcs = 0, rv = 1"""
+    d = Dci2(format, alloc_type, type0_alloc, type1_subset, type1_shift, type1_bitmap, tpc_pucch, harq_process,
+             tb_cw_swap)
+    for t, (mcs, ndi, rv) in enumerate(tb):
+        d.tb[t] = _Dci2Tb(mcs, ndi, rv, int(not (mcs == 0 and rv == 1)))
+    d.pinfo = pinfo
+    return d
+
+
+def dci2_size(format, nof_prb, nof_ports=2):
+    n = lib().mi_dci_dl2_size(format, nof_prb, nof_ports)
+    if n < 0:
+        raise ValueError("mi_dci_dl2_size: " + last_error())
+    return n
+
+
+def dci2_pack(nof_prb, d, nof_ports=2):
+    """payload bits (one per byte, MSB first) of a Dci2"""
+    bits = np.zeros(64, np.uint8)
+    n = lib().mi_dci_dl2_pack(nof_prb, nof_ports, C.byref(d), bits.ctypes.data)
+    if n < 0:
+        raise ValueError("mi_dci_dl2_pack: " + last_error())
+    return bits[:n].copy()
+
+
+def dci2_unpack(format, nof_prb, bits, nof_ports=2):
+    b = np.ascontiguousarray(bits, np.uint8)
+    d = Dci2()
+    if lib().mi_dci_dl2_unpack(format, nof_prb, nof_ports, b.ctypes.data, len(b), C.byref(d)):
+        raise ValueError("mi_dci_dl2_unpack: " + last_error())
+    return d
+
+
+def dci2_to_cfgs(d, base, new_tb=(1, 1), reported_cb_r2=0):
+    """the one or two batch entries (SfCfg) that decode grant d in the subframe of base (mi_dci_dl2_to_cfg)"""
+    out = (SfCfg * 2)()
+    nt = np.array(new_tb, np.uint8)
+    n = lib().mi_dci_dl2_to_cfg(C.byref(d), C.byref(base), nt.ctypes.data, reported_cb_r2, C.cast(out, C.c_void_p))
+    if n < 0:
+        raise ValueError("mi_dci_dl2_to_cfg: " + last_error())
+    res = []
+    for i in range(n):
+        c = SfCfg()
+        C.memmove(C.byref(c), C.byref(out[i]), C.sizeof(SfCfg))
+        res.append(c)
+    return res
+
+
+def emu_pdcch_llr_rx(cell_id, nof_prb, nof_ports, phich_ng, cfi, sf_idx, grids, ces, noise=0.0):
+    """TEST-ONLY: the PDCCH soft bits (logical order) of one subframe from the host emulation of the antenna-combining
+    pdcch_llr_kernel; grids [n_rx][14][12 nof_prb], ces [n_rx][ports][14][12 nof_prb], complex"""
+    g = np.ascontiguousarray(grids, np.complex64)
+    h = np.ascontiguousarray(ces, np.complex64)
+    n_rx = g.shape[0]
+    if g.size != n_rx * 14 * 12 * nof_prb or h.size != g.size * nof_ports:
+        raise ValueError("emu_pdcch_llr_rx: arrays do not match the configuration")
+    out = np.zeros(8 * 12 * nof_prb, np.float32)   # at most 3 REGs per PRB in each of at most 4 control symbols
+    M = emu().emu_pdcch_llr_rx(cell_id, nof_prb, nof_ports, phich_ng, cfi, sf_idx, n_rx, g.ctypes.data, h.ctypes.data,
+                               float(noise), out.ctypes.data)
+    if M < 0:
+        raise ValueError("emu_pdcch_llr_rx: bad configuration")
+    return out[:8 * M].copy()
 
 
 CSI_NHYP, CSI_MAX_SB = 8, 14

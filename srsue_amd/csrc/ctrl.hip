@@ -7,6 +7,12 @@
 // decisions are bit-identical on identical soft bits).
 //
 // MI355X layout:
+//   * every kernel that reads the grid has a two-antenna form (template argument NRX = 2: a two-antenna batch's control
+//     object created with MI_CTRL_FLAG_RX_COMBINE): the equalisers combine both antenna planes per RE (ctrl_rx_body.h),
+//     everything after the equalised symbols is the one-antenna code.  The thread shapes are the one-antenna ones: a
+//     PDCCH thread's loads of both antennas (2 x 12 scattered 8-byte loads with two ports) are independent and issued
+//     together, and at 0.06 ms of a 3.9 ms step the stage is not worth a second shape.  NRX = 1 is the code as it
+//     was (eq_quad / eq_tm1 / eq_tm2 of ctrl_dev.h); g_rx / c_rx are unused there
 //   * pcfich_kernel: one wavefront per subframe (16 REs, 32 soft bits, 3 code-word correlations);
 //   * pdcch_llr_kernel: one thread per REG (4 REs -> 8 soft bits), REG -> logical quadruplet and the
 //     scrambling words from per-(cell, sf, cfi) tables; writes the soft bits in logical CCE order;
@@ -34,9 +40,11 @@ __device__ __forceinline__ void eq_quad(const float2* g, const float2* c0, const
   }
 }
 
+template <int NRX>
 __global__ __launch_bounds__(64) void pcfich_kernel(const float2* __restrict__ grid, const float2* __restrict__ ce,
                                                    const MiCtrlSf* __restrict__ sfs,
-                                                   const uint32_t* __restrict__ cdata, uint32_t* __restrict__ cfi) {
+                                                   const uint32_t* __restrict__ cdata, uint32_t* __restrict__ cfi,
+                                                   size_t g_rx, size_t c_rx) {
   __shared__ float llr[32];
   const MiCtrlSf d = sfs[blockIdx.x];
   const uint32_t t = threadIdx.x;
@@ -47,7 +55,8 @@ __global__ __launch_bounds__(64) void pcfich_kernel(const float2* __restrict__ g
   const uint32_t sc = cdata[d.pcfich_off + 16];   // 32 scrambling bits
   if (t < 4) {
     float2 x[4];
-    eq_quad(g, c0, c1, k16 + 4 * t, d.ports == 2, 0.0f, x);
+    if constexpr (NRX == 1) eq_quad(g, c0, c1, k16 + 4 * t, d.ports == 2, 0.0f, x);
+    else eq_quad_rx<NRX>(g, c0, c1, k16 + 4 * t, d.ports == 2, 0.0f, g_rx, c_rx, x);
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       float l[2];
@@ -74,10 +83,11 @@ __global__ __launch_bounds__(64) void pcfich_kernel(const float2* __restrict__ g
   }
 }
 
+template <int NRX>
 __global__ __launch_bounds__(256) void pdcch_llr_kernel(const float2* __restrict__ grid, const float2* __restrict__ ce,
                                                        const MiCtrlSf* __restrict__ sfs,
                                                        const uint32_t* __restrict__ cdata, float* __restrict__ llr,
-                                                       float noise) {
+                                                       float noise, size_t g_rx, size_t c_rx) {
   const MiCtrlSf d = sfs[blockIdx.y];
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= d.M) return;
@@ -86,6 +96,11 @@ __global__ __launch_bounds__(256) void pdcch_llr_kernel(const float2* __restrict
   const float2* c1 = c0 + d.plane;
   const uint32_t* re = cdata + d.reg_off + 4 * i;
   const uint32_t lg = cdata[d.reg_off + 4 * d.M + i];
+  if constexpr (NRX != 1) {
+    const uint32_t sw = cdata[d.scr_off + lg / 4] >> (8 * (lg % 4));
+    pdcch_reg_llr_rx<NRX>(g, c0, c1, re, d.ports == 2, noise, g_rx, c_rx, sw, llr + d.llr_off + 8 * lg);
+    return;
+  }
   float2 x[4];
   eq_quad(g, c0, c1, re, d.ports == 2, noise, x);
   const uint32_t sw = cdata[d.scr_off + lg / 4] >> (8 * (lg % 4));   // 8 scrambling bits of quadruplet lg
@@ -134,9 +149,11 @@ __global__ __launch_bounds__(64) void dci_search_kernel(const float* __restrict_
 // PHICH (36.211 6.9): one wavefront per subframe; lanes equalise the group's 12 REs (SFBC: 6 pairs),
 // lane 0 despreads them in order i = 0..11 (oracle or_phich_soft's contract, in fp32):
 // s = sum_i Re(conj(w(i mod 4)) (1 - 2 c(i)) x(i) (1 - j) / sqrt2), soft HI = -s (> 0 favours ACK)
+template <int NRX>
 __global__ __launch_bounds__(64) void phich_kernel(const float2* __restrict__ grid, const float2* __restrict__ ce,
                                                   const MiCtrlSf* __restrict__ sfs,
-                                                  const uint32_t* __restrict__ cdata, float* __restrict__ soft) {
+                                                  const uint32_t* __restrict__ cdata, float* __restrict__ soft,
+                                                  size_t g_rx, size_t c_rx) {
   __shared__ float2 x[12];
   const MiCtrlSf d = sfs[blockIdx.x];
   const uint32_t t = threadIdx.x;
@@ -148,10 +165,13 @@ __global__ __launch_bounds__(64) void phich_kernel(const float2* __restrict__ gr
     if (t < 6) {
       float2 a, b;
       const uint32_t r0 = re[2 * t], r1 = re[2 * t + 1];
-      eq_tm2(g[r0], g[r1], c0[r0], c0[r1], c1[r0], c1[r1], a, b);
+      if constexpr (NRX == 1) eq_tm2(g[r0], g[r1], c0[r0], c0[r1], c1[r0], c1[r1], a, b);
+      else eq_pair_rx<NRX>(g, c0, c1, r0, r1, g_rx, c_rx, &a, &b);
       x[2 * t] = a;
       x[2 * t + 1] = b;
     }
+  } else if (NRX != 1) {
+    if (t < 12) x[t] = eq_re_rx<NRX, true>(g, c0, re[t], 0.0f, g_rx, c_rx);
   } else if (t < 12) {
     const float2 h = c0[re[t]];
     float den = h.x * h.x + h.y * h.y;
@@ -177,21 +197,30 @@ __global__ __launch_bounds__(64) void phich_kernel(const float2* __restrict__ gr
 }
 
 void launch_phich(const float2* grid, const float2* ce, const MiCtrlSf* sfs, const uint32_t* cdata, float* soft,
-                  uint32_t n_sf, hipStream_t st) {
+                  uint32_t n_sf, hipStream_t st, const CtrlRx& rx) {
   if (!n_sf) return;
-  hipLaunchKernelGGL(phich_kernel, dim3(n_sf), dim3(64), 0, st, grid, ce, sfs, cdata, soft);
+  if (rx.n_rx == 2)
+    hipLaunchKernelGGL(phich_kernel<2>, dim3(n_sf), dim3(64), 0, st, grid, ce, sfs, cdata, soft, rx.g_rx, rx.c_rx);
+  else
+    hipLaunchKernelGGL(phich_kernel<1>, dim3(n_sf), dim3(64), 0, st, grid, ce, sfs, cdata, soft, (size_t)0, (size_t)0);
 }
 
 void launch_pcfich(const float2* grid, const float2* ce, const MiCtrlSf* sfs, const uint32_t* cdata, uint32_t* cfi,
-                   uint32_t n_sf, hipStream_t st) {
+                   uint32_t n_sf, hipStream_t st, const CtrlRx& rx) {
   if (!n_sf) return;
-  hipLaunchKernelGGL(pcfich_kernel, dim3(n_sf), dim3(64), 0, st, grid, ce, sfs, cdata, cfi);
+  if (rx.n_rx == 2)
+    hipLaunchKernelGGL(pcfich_kernel<2>, dim3(n_sf), dim3(64), 0, st, grid, ce, sfs, cdata, cfi, rx.g_rx, rx.c_rx);
+  else
+    hipLaunchKernelGGL(pcfich_kernel<1>, dim3(n_sf), dim3(64), 0, st, grid, ce, sfs, cdata, cfi, (size_t)0, (size_t)0);
 }
 void launch_pdcch_llr(const float2* grid, const float2* ce, const MiCtrlSf* sfs, const uint32_t* cdata, float* llr,
-                      uint32_t n_sf, uint32_t max_regs, float noise, hipStream_t st) {
+                      uint32_t n_sf, uint32_t max_regs, float noise, hipStream_t st, const CtrlRx& rx) {
   if (!n_sf || !max_regs) return;
-  hipLaunchKernelGGL(pdcch_llr_kernel, dim3((max_regs + 255) / 256, n_sf), dim3(256), 0, st, grid, ce, sfs, cdata, llr,
-                     noise);
+  const dim3 grd((max_regs + 255) / 256, n_sf);
+  if (rx.n_rx == 2)
+    hipLaunchKernelGGL(pdcch_llr_kernel<2>, grd, dim3(256), 0, st, grid, ce, sfs, cdata, llr, noise, rx.g_rx, rx.c_rx);
+  else
+    hipLaunchKernelGGL(pdcch_llr_kernel<1>, grd, dim3(256), 0, st, grid, ce, sfs, cdata, llr, noise, (size_t)0, (size_t)0);
 }
 void launch_dci_search(const float* llr, const MiDciJob* jobs, const uint32_t* cdata, MiDciRes* res, uint32_t n_jobs,
                        hipStream_t st) {

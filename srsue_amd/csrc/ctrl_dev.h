@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ctrl_rx_body.h"
+
 namespace mi {
 
 __device__ __forceinline__ void eq_tm1(float2 y, float2 h, float noise, float2& x) {
@@ -25,12 +27,7 @@ __device__ __forceinline__ void eq_tm2(float2 r0, float2 r1, float2 h00, float2 
   x1.y = s * (-(h10.y * r0.x - h10.x * r0.y) + (h01.x * r1.y - h01.y * r1.x));
 }
 
-// QPSK max-log soft bits, LLR > 0 => bit 1 (same scale as the PDSCH demapper)
-__device__ __forceinline__ void qpsk_llr(float2 x, float* l) {
-  const float a = 0.70710678118f;
-  l[0] = ((x.x - a) * (x.x - a) - (x.x + a) * (x.x + a)) * 2.0f;
-  l[1] = ((x.y - a) * (x.y - a) - (x.y + a) * (x.y + a)) * 2.0f;
-}
+// the QPSK demapper qpsk_llr: ctrl_rx_body.h (one definition for these kernels and the host emulation)
 
 // generators 133, 171, 165 (octal): bit 6 <-> c_k, bit 0 <-> c_{k-6}
 __device__ __forceinline__ int par7(uint32_t x) { return __popc(x) & 1; }

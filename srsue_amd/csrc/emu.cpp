@@ -13,11 +13,13 @@
 #include <vector>
 
 #include "csi_body.h"
+#include "ctrl_rx_body.h"
 #include "demap_body.h"
 #include "kernels_consts.h"
 #include "plan.h"
 #include "rm_body.h"
 #include "sm_body.h"
+#include "tables.h"
 #include "tb_body.h"
 #include "tdec_body.h"
 #include "tdec_p2_body.h"
@@ -424,6 +426,37 @@ extern "C" int emu_pdsch_llr_sm(const mi_dl_sf_cfg_t* cfg_pair, const float* gri
   memcpy(out0, &e[d.e0], (size_t)d.nre * d.qm0 * sizeof(float));
   memcpy(out1, &e[d.e1], (size_t)d.nre * d.qm1 * sizeof(float));
   return (int)d.nre;
+}
+
+// The 8 M PDCCH soft bits of one subframe, in logical (CCE) order, from n_rx antennas' grids ([n_rx][14][W] float2) and
+// channel estimates ([n_rx][ports][14][W] float2): ctrl_rx_body.h pdcch_reg_llr_rx -- the arithmetic of the two-antenna
+// pdcch_llr_kernel, REG by REG -- over the planner's REG list, quadruplet permutation and scrambling words (tables.cpp,
+// as CtrlEngine::build lays them out).  out: 8 M floats.  Returns M, -1 on a bad cell, CFI or antenna count.
+template <int NRX>
+static void emu_pdcch_run(uint32_t M, uint32_t ports, size_t W, const float2* g, const float2* c0, const uint32_t* re,
+                          const uint32_t* lg, const uint32_t* scr, float noise, float* out) {
+  const size_t g_rx = (size_t)mi::NSYMB * W, c_rx = g_rx * ports;
+  for (uint32_t i = 0; i < M; i++) {
+    const uint32_t q = lg[i], sw = scr[q / 4] >> (8 * (q % 4));
+    mi::pdcch_reg_llr_rx<NRX>(g, c0, c0 + g_rx, re + 4 * i, ports == 2, noise, g_rx, c_rx, sw, out + 8 * (size_t)q);
+  }
+}
+extern "C" int emu_pdcch_llr_rx(uint32_t cell_id, uint32_t nof_prb, uint32_t nof_ports, uint32_t phich_ng, uint32_t cfi,
+                                uint32_t sf_idx, uint32_t n_rx, const float* grids, const float* ces, float noise,
+                                float* out) {
+  if (n_rx < 1 || n_rx > 2 || nof_ports < 1 || nof_ports > 2 || cfi < 1 || cfi > 3 || phich_ng > 3 || sf_idx > 9 ||
+      cell_id > 503 || !mi::std_nof_prb(nof_prb))
+    return -1;
+  std::vector<uint32_t> re4, lg;
+  const uint32_t M = mi::pdcch_regs(cell_id, nof_prb, phich_ng, cfi, &re4);
+  mi::pdcch_quad_perm(M, cell_id, lg);
+  std::vector<uint32_t> scr((8 * M + 31) / 32);
+  mi::gold_words(sf_idx * 512 + cell_id, 8 * M, scr.data());
+  const float2* g = reinterpret_cast<const float2*>(grids);
+  const float2* c0 = reinterpret_cast<const float2*>(ces);
+  if (n_rx == 2) emu_pdcch_run<2>(M, nof_ports, 12 * (size_t)nof_prb, g, c0, re4.data(), lg.data(), scr.data(), noise, out);
+  else emu_pdcch_run<1>(M, nof_ports, 12 * (size_t)nof_prb, g, c0, re4.data(), lg.data(), scr.data(), noise, out);
+  return (int)M;
 }
 
 // The CSI record of one subframe (csi_body.h: the arithmetic of csi_kernel, point by point) from its channel estimates

@@ -349,8 +349,14 @@ uint32_t dci_size(int format, uint32_t nof_prb) {
   uint32_t n01a = 15 + rba;   // 1A = 15 + RBA >= format 0 = 14 + RBA (FDD)
   if (dci_ambiguous(n01a)) n01a++;
   if (format == DCI_1C) return (nof_prb >= 50 ? 1 : 0) + dci1c_rba_bits(nof_prb) + 5;   // 36.212 5.3.3.1.4
+  const uint32_t P = rbg_size(nof_prb);
+  if (format == DCI_2 || format == DCI_2A) {
+    // 36.212 5.3.3.1.5 / 5.3.3.1.5A, 2 ports: [RA header], RBG bits, TPC 2, HARQ 3, swap 1, 2 x (MCS 5, NDI 1, RV 2),
+    // precoding information 3 / 0; one zero bit when the size is one of Table 5.3.3.1.2-1 (no 0/1A comparison)
+    const uint32_t s2 = (nof_prb > 10 ? 1 : 0) + (nof_prb + P - 1) / P + 22 + (format == DCI_2 ? 3 : 0);
+    return dci_ambiguous(s2) ? s2 + 1 : s2;
+  }
   if (format != DCI_1) return n01a;
-  const uint32_t P = nof_prb <= 10 ? 1 : nof_prb <= 26 ? 2 : nof_prb <= 63 ? 3 : 4;
   uint32_t s1 = (nof_prb > 10 ? 1 : 0) + (nof_prb + P - 1) / P + 13;
   // 36.212 5.3.3.1.2: pad until neither the 0/1A size nor one of Table 5.3.3.1.2-1
   while (s1 == n01a || dci_ambiguous(s1)) s1++;
@@ -358,6 +364,34 @@ uint32_t dci_size(int format, uint32_t nof_prb) {
 }
 
 uint32_t rbg_size(uint32_t nof_prb) { return nof_prb <= 10 ? 1 : nof_prb <= 26 ? 2 : nof_prb <= 63 ? 3 : 4; }
+
+int ra_type01_prbs(uint32_t nof_prb, bool type1, uint32_t type0_alloc, uint32_t subset, uint32_t shift,
+                   uint32_t bitmap, uint8_t* prb) {
+  const uint32_t N = nof_prb, P = rbg_size(N), nrbg = (N + P - 1) / P;
+  memset(prb, 0, N);
+  if (!type1) {
+    for (uint32_t g = 0; g < nrbg; g++)
+      if ((type0_alloc >> (nrbg - 1 - g)) & 1u)
+        for (uint32_t p = g * P; p < (g + 1) * P && p < N; p++) prb[p] = 1;
+  } else {
+    // type 1 (36.213 7.1.6.2): subset p, shift, bitmap over N_RB^TYPE1 VRBs of the subset
+    const uint32_t pb = ceil_log2(P), nt1 = nrbg - pb - 1, sp = subset;
+    if (sp >= P) return -1;
+    // VRBs in subset p: full RBG rows below the last RBG's subset, the partial last one, none above
+    const uint32_t last = (N - 1) / P % P, rows = (N - 1) / (P * P);
+    const uint32_t n_sub = sp < last ? rows * P + P : sp == last ? rows * P + (N - 1) % P + 1 : rows * P;
+    const uint32_t delta = shift ? (n_sub > nt1 ? n_sub - nt1 : 0) : 0;
+    for (uint32_t i = 0; i < nt1; i++) {
+      if (!((bitmap >> (nt1 - 1 - i)) & 1u)) continue;
+      const uint32_t j = i + delta, p = (j / P) * P * P + sp * P + j % P;
+      if (j >= n_sub || p >= N) return -1;
+      prb[p] = 1;
+    }
+  }
+  int n = 0;
+  for (uint32_t p = 0; p < N; p++) n += prb[p];
+  return n;
+}
 
 uint32_t n_gap(uint32_t nof_prb, bool gap2) {
   if (gap2) return nof_prb < 50 ? 0 : nof_prb < 64 ? 9 : 16;

@@ -50,11 +50,17 @@ inline uint32_t phich_cinit(uint32_t id, uint32_t sf) { return (sf + 1) * (2 * i
 uint32_t pdcch_regs(uint32_t id, uint32_t nof_prb, uint32_t ng, uint32_t cfi, std::vector<uint32_t>* re4);
 // logical quadruplet carried by each physical REG (quadruplet sub-block interleaver + shift by N_ID)
 void pdcch_quad_perm(uint32_t M, uint32_t id, std::vector<uint32_t>& log_of_reg);
-enum { DCI_0 = 0, DCI_1 = 1, DCI_1A = 2, DCI_1C = 3 };
+enum { DCI_0 = 0, DCI_1 = 1, DCI_1A = 2, DCI_1C = 3, DCI_2 = 4, DCI_2A = 5 };
+// DCI_2 / DCI_2A: the two-port sizes (36.212 5.3.3.1.5 / 5.3.3.1.5A: 3 / 0 precoding-information bits)
 uint32_t dci_size(int format, uint32_t nof_prb);
 // ---- DL resource allocation (36.213 7.1.6, 36.211 6.2.3.2) -------------------------------------
 uint32_t ceil_log2(uint32_t x);
 uint32_t rbg_size(uint32_t nof_prb);                       // Table 7.1.6.1-1
+// PRBs of a type 0 (RBG bitmap, MSB = RBG 0) or type 1 (subset, shift, bitmap: 36.213 7.1.6.2) allocation, the one
+// code behind formats 1, 2 and 2A: prb[p] = 1 for every allocated PRB p < nof_prb (prb is zeroed first).  Returns the
+// PRB count, -1 for a subset >= P or a bitmap bit outside the subset
+int ra_type01_prbs(uint32_t nof_prb, bool type1, uint32_t type0_alloc, uint32_t subset, uint32_t shift,
+                   uint32_t bitmap, uint8_t* prb);
 uint32_t n_gap(uint32_t nof_prb, bool gap2);               // Table 6.2.3.2-1 (0: not defined)
 uint32_t n_vrb_dist(uint32_t nof_prb, bool gap2);          // N_VRB^DL of the distributed mapping
 // PRB of distributed VRB n_vrb in slot 0 / 1; -1 outside N_VRB^DL

@@ -571,32 +571,21 @@ int srslte_dci_msg_to_dl_grant(srslte_dci_msg_t* msg, uint16_t msg_rnti, uint32_
     dci->dci_format = SRSLTE_DCI_FORMAT1;
     if (!type1) {
       dci->alloc_type = SRSLTE_RA_ALLOC_TYPE0;
-      for (uint32_t g = 0; g < nrbg; g++) {
-        const uint32_t bit = take_bits(msg->data, &pos, 1);
-        dci->type0_alloc = (dci->type0_alloc << 1) | bit;
-        for (uint32_t p = g * P; bit && p < (g + 1) * P && p < N; p++) grant->prb_idx[0][p] = grant->prb_idx[1][p] = true;
-      }
+      dci->type0_alloc = take_bits(msg->data, &pos, nrbg);
     } else {
-      // type 1 (36.213 7.1.6.2): subset p, shift, bitmap over N_RB^TYPE1 VRBs of the subset
       dci->alloc_type = SRSLTE_RA_ALLOC_TYPE1;
       const uint32_t pb = mi::ceil_log2(P), nt1 = nrbg - pb - 1;
       dci->type1_subset = take_bits(msg->data, &pos, pb);
       dci->type1_shift = take_bits(msg->data, &pos, 1);
       dci->type1_bitmap = take_bits(msg->data, &pos, nt1);
-      const uint32_t sp = dci->type1_subset;
-      if (sp >= P) return SRSLTE_ERROR;
-      // VRBs in subset p: full RBG rows below the last RBG's subset, the partial last one, none above
-      const uint32_t last = (N - 1) / P % P, rows = (N - 1) / (P * P);
-      const uint32_t n_sub = sp < last ? rows * P + P : sp == last ? rows * P + (N - 1) % P + 1 : rows * P;
-      const uint32_t delta = dci->type1_shift ? (n_sub > nt1 ? n_sub - nt1 : 0) : 0;
-      for (uint32_t i = 0; i < nt1; i++) {
-        if (!((dci->type1_bitmap >> (nt1 - 1 - i)) & 1u)) continue;
-        const uint32_t j = i + delta, p = (j / P) * P * P + sp * P + j % P;
-        if (j >= n_sub || p >= N) return SRSLTE_ERROR;
-        grant->prb_idx[0][p] = grant->prb_idx[1][p] = true;
-      }
     }
-    for (uint32_t p = 0; p < N; p++) grant->nof_prb += grant->prb_idx[0][p] ? 1 : 0;
+    // type 0 / type 1 -> PRBs: the code formats 2 / 2A share (tables.cpp)
+    uint8_t prb[SRSLTE_MAX_PRB];
+    const int n = mi::ra_type01_prbs(N, type1, dci->type0_alloc, dci->type1_subset, dci->type1_shift ? 1 : 0,
+                                     dci->type1_bitmap, prb);
+    if (n < 0) return SRSLTE_ERROR;
+    for (uint32_t p = 0; p < N; p++) grant->prb_idx[0][p] = grant->prb_idx[1][p] = prb[p] != 0;
+    grant->nof_prb = (uint32_t)n;
     if (!grant->nof_prb) return SRSLTE_ERROR;
     nprb_tbs = grant->nof_prb;
   } else {
